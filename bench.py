@@ -1,7 +1,12 @@
 """Benchmark: CIFAR-10 UNet DDPM training img/s (BASELINE.json metric), plus DDIM-50 sampling img/s.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K train steps and prints the headline JSON line; everything listed under
+"--full" below (side lines that take runs of their own) is measured only with --full. `--dump-outputs DIR` writes
+what the last timed step handed its caller (dump_outputs) as DIR/<name>.npy; with the same arguments the weights,
+batches and random draws are the same from run to run, so two builds can be compared output for output.
 
 A "step" is one full DiffusionTrainer.train_step of the reference loop (utils/trainer.py:222-265) on a
 synthetic 128 x 3 x 32 x 32 batch already resident in HBM: t ~ randint, q_sample, UNet forward, MSE,
@@ -10,7 +15,7 @@ dropout 0.1, on the configs/cifar10_unet.py network (37.06 M params, random init
 Data parallel: one process per GPU, gradients averaged by RCCL all-reduce overlapped with backward; each
 rank trains its own 128-image shard (weak scaling). value = images of all ranks / max-over-ranks time.
 
-The JSON line also carries:
+With --full the JSON line also carries:
   roofline      the dominant kernel (implicit-GEMM 3x3 conv, bf16 MFMA): achieved = algorithmic FLOPs per
                 launch / average launch time, vs the 2.5 PFLOP/s dense bf16 MFMA peak (MI355X_MICROARCH.md);
                 the headline uses the rocprofv3 kernel-trace average committed under profiles/ for this tree,
@@ -27,8 +32,8 @@ The JSON line also carries:
                 fed by it, and the oracle's per-sample transform on one host thread as its CPU baseline
   dit_s2_ddim50_cfg  BASELINE config #4: DiT-S/2 conditional DDIM-50 + CFG 3.0 sampling img/s (replicas) with
                 its MFMA roofline, and the DiT train step img/s (--no-dit skips it)
-(celeba64 / fp32 only at N=1; --no-extra skips them.) `--image-size 64 --sample-steps 100` makes config #5 the
-headline line instead.
+(celeba64 / fp32 only at N=1; --no-extra skips them; the --no-* options trim a --full run.) `--image-size 64
+--sample-steps 100` makes config #5 the headline line instead.
 """
 import argparse
 import json
@@ -271,7 +276,7 @@ def train_rate(trainer, pool, steps, warmup, world):
     r0 = g.replays if g is not None else 0
     t0 = time.perf_counter()
     for i in range(steps):
-        trainer.train_step(pool[i % len(pool)], 0)
+        loss = trainer.train_step(pool[i % len(pool)], 0)
     host_el = time.perf_counter() - t0      # until the last train_step returned (the GPU may still be running)
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
@@ -279,6 +284,7 @@ def train_rate(trainer, pool, steps, warmup, world):
     # until step k-4 has run, i.e. paces the host to the GPU)
     ring = (g.ring_wait_s - w0) if g is not None else 0.0
     trainer._bench_graphed = g is not None and g.replays - r0 == steps   # every timed step was a graph replay
+    trainer._bench_last_loss = loss if steps > 0 else None                # what the last timed step returned
     return max_over_ranks(el, world), (host_el - ring, ring)
 
 
@@ -297,6 +303,28 @@ def exposed_comm(trainer, pool, steps=5):
     finally:
         g.measure_comm = False
     return v
+
+
+DUMP_SAMPLE = 4 * 1024 * 1024      # elements kept of a larger flattened state (16 MB as float32)
+
+
+def dump_outputs(path, trainer):
+    """--dump-outputs: what the last timed train_step handed its caller, as float32 .npy files under `path`:
+    loss.npy (the scalar it returned), params.npy and ema_params.npy (the state it left behind: the model's and the
+    EMA model's parameters, flattened and concatenated in parameters() order). A state of more than DUMP_SAMPLE
+    elements is cut to a fixed sample (indices from numpy's default_rng(0), sorted), so the same positions are
+    compared between two builds."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    loss = trainer._bench_last_loss
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().cpu().numpy().reshape(1))
+    for name, mod in (("params", trainer._module), ("ema_params", trainer.ema_model)):
+        if mod is None:
+            continue
+        flat = torch.cat([p.detach().float().reshape(-1) for p in mod.parameters()]).cpu().numpy()
+        if flat.size > DUMP_SAMPLE:
+            flat = flat[np.sort(np.random.default_rng(0).integers(0, flat.size, DUMP_SAMPLE))]
+        np.save(os.path.join(path, name + ".npy"), flat)
 
 
 def max_over_ranks(v, world):
@@ -393,9 +421,10 @@ def rccl_one_rank_line(args, base_ms):
     (`bench.py --dist-one-rank`): a failure inside RCCL or its watchdog thread aborts that process, never the
     headline run."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--dist-one-rank", "--dist-force-avg", "--no-sample", "--no-extra",
-           "--no-dit", "--no-cpu", "--no-roofline", "--steps", str(args.steps), "--warmup", str(args.warmup),
-           "--dtype", args.dtype, "--batch", str(args.batch), "--image-size", str(args.image_size)]
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--dist-one-rank", "--dist-force-avg", "--no-sample",
+           "--no-extra", "--no-dit", "--no-cpu", "--no-roofline", "--steps", str(args.steps),
+           "--warmup", str(args.warmup), "--dtype", args.dtype, "--batch", str(args.batch),
+           "--image-size", str(args.image_size)]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     if r.returncode != 0:
@@ -487,6 +516,11 @@ def main():
                     help="profiling: the headline step through GradSync + the segmented graph on a 1-rank RCCL group")
     ap.add_argument("--dist-force-avg", action="store_true",
                     help="with --dist-one-rank: all-reduce with ReduceOp.AVG (the multi-rank op) instead of SUM")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the side lines (sampling, DiT, 64x64, fp32, data loader, one-rank RCCL, conv "
+                         "roofline, CPU baselines, exposed communication); the --no-* options trim this set")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned and left behind as DIR/<name>.npy (float32)")
     args = ap.parse_args()
     if args.dit_only:
         torch.cuda.set_device(0)
@@ -495,6 +529,12 @@ def main():
     if args.roofline_only:
         print(json.dumps(conv_roofline(torch.bfloat16 if args.dtype == "bf16" else torch.float32)), flush=True)
         return
+    if not args.full:
+        # a plain run: set up, warm up, time the steps, print the headline line
+        if args.no_train:
+            ap.error("--no-train leaves only side lines to measure: it needs --full")
+        args.no_sample = args.no_cpu = args.no_roofline = True
+        args.extra = args.dit = False
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -540,6 +580,8 @@ def main():
     ms = el / args.steps * 1e3
     value = world * B * args.steps / el
     log(f"[bench] rank {rank}: {ms:.2f} ms/step, {value:.1f} img/s aggregate")
+    if args.dump_outputs and rank == 0 and not args.no_train:
+        dump_outputs(args.dump_outputs, trainer)
     gflop = TRAIN_GFLOP_PER_IMG * (S / 32) ** 2
 
     name = "CIFAR-10" if S == 32 else f"CelebA {S}x{S}"
@@ -575,7 +617,7 @@ def main():
             out["comm_in_graph"] = bool(trainer._graph.comm_in_graph)
             if trainer._graph.capture_fallback:
                 out["comm_capture_fallback"] = trainer._graph.capture_fallback
-        if not args.no_train:
+        if args.full and not args.no_train:
             # the part of the gradient all-reduce the backward did not hide (measured after the timed region)
             v = exposed_comm(trainer, pool)
             out["exposed_comm_ms_per_step"] = None if v is None else round(max_over_ranks(v, world), 4)

@@ -5,7 +5,7 @@
 #
 # 1. if TESTS is set: the GPU tests it selects (pytest args, e.g. "-k wgrad" or "tests/test_gpu_dit.py") run once
 #    first (parity before timing);
-# 2. one bench.py run per setting (BENCH_ARGS, default: the headline train + DDIM-50 + CFG lines), repeated
+# 2. one bench.py run per setting (BENCH_ARGS, default: --full trimmed to the train + DDIM-50 + CFG lines), repeated
 #    REPS times (default 1) in interleaved order so box drift hits every arm alike; one summary line per run.
 # A setting may point DMC_LIB at another build of libdmc.so (e.g. the previous commit's) for a same-box regression.
 set -e -o pipefail
@@ -17,7 +17,7 @@ if [ -n "$TESTS" ]; then
     || { tail -30 "$O/tests.log"; exit 1; }
   tail -1 "$O/tests.log"
 fi
-ARGS=${BENCH_ARGS:---no-extra --no-dit --no-cpu --no-roofline}
+ARGS=${BENCH_ARGS:---full --no-extra --no-dit --no-cpu --no-roofline}
 i=0
 for rep in $(seq 1 ${REPS:-1}); do
   for cfg in "$@"; do

@@ -14,7 +14,7 @@ D=(python3 bench.py --dit-only --no-train)
 timeout -s KILL 400 rocprofv3 --pmc FETCH_SIZE -d $O/dtf -o f --output-format csv -- "${D[@]}" > $O/dtf.log 2>&1 || { tail $O/dtf.log; exit 1; }
 timeout -s KILL 400 rocprofv3 --pmc WRITE_SIZE -d $O/dtw -o w --output-format csv -- "${D[@]}" > $O/dtw.log 2>&1 || { tail $O/dtw.log; exit 1; }
 python3 scripts/pmc_loop.py $O/dtf $O/dtw 2 $O/pmc_dit_loop.json
-S=(python3 bench.py --no-train --no-cpu --no-cfg --no-extra --no-dit --no-roofline)
+S=(python3 bench.py --full --no-train --no-cpu --no-cfg --no-extra --no-dit --no-roofline)
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/smp -o smp --output-format csv -- "${S[@]}" > $O/smp.log 2>&1 || { tail $O/smp.log; exit 1; }
 T=(python3 bench.py --no-sample --no-cpu --no-cfg --no-extra --no-dit --no-roofline)
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/trn -o trn --output-format csv -- "${T[@]}" > $O/trn.log 2>&1 || { tail $O/trn.log; exit 1; }

@@ -7,7 +7,7 @@ timeout -k 10 400 python -u -m pytest -x -v --timeout 200 --timeout-method threa
   tests/test_gpu_model.py -k "gn_stats_apply or stats_one_block or small_map_gn or halo_prologue_bitwise" \
   > $O/tests.log 2>&1 || { tail -40 $O/tests.log; exit 1; }
 tail -2 $O/tests.log
-A="--no-cpu --no-extra --no-dit --no-roofline --no-cfg"
+A="--full --no-cpu --no-extra --no-dit --no-roofline --no-cfg"
 for r in 1 2; do
   for on in 8192 0; do
     timeout -k 10 300 python3 -c "

@@ -3,7 +3,7 @@
 # that touch the Python executor and the C ABI together, where DMC_LIB alone cannot select the old behaviour)
 set -o pipefail
 O=$PWD/gpurun_out/${1:-r6dirab}; mkdir -p $O
-ARGS=${BENCH_ARGS:---no-extra --no-dit --no-cpu --no-roofline}
+ARGS=${BENCH_ARGS:---full --no-extra --no-dit --no-cpu --no-roofline}
 for rep in 1 2; do
   for arm in prev new; do
     d=.; [ $arm = prev ] && d=_ab_prev
