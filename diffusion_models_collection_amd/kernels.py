@@ -471,6 +471,15 @@ def add_(dtype, y, x):
     check(LIB.dmc_add(L.dtype_code(dtype), ptr(y), ptr(x), y.numel(), L.stream()), "dmc_add")
 
 
+def silu_fwd(x, out=None):
+    """y = x * sigmoid(x) of a contiguous fp32 tensor (dmc_silu_fwd)."""
+    if out is None:
+        out = torch.empty_like(x)
+    _same(x, out, what="dmc_silu_fwd")
+    check(LIB.dmc_silu_fwd(ptr(x), ptr(out), x.numel(), L.stream()), "dmc_silu_fwd")
+    return out
+
+
 def q_sample(x0, noise, t, a, b, out=None):
     x0 = x0.contiguous()
     noise = noise.contiguous()
@@ -523,12 +532,12 @@ def ddpm_step(x, eps, t, sra, srm1, c1, c2, logvar, clip=True, x0=None, z=None, 
     return out
 
 
-def cfg_x0(x, ec, eu, scale, t, ta, tb, mode, p_threshold):
+def cfg_x0(x, ec, eu, scale, t, ta, tb, mode, p_threshold, out=None):
+    """(eps, x0) of the guided step; out: the two buffers to fill (allocated if None)."""
     N = x.shape[0]
-    _same(x, ec, eu, what="dmc_cfg_x0")
+    eps, x0 = out if out is not None else (torch.empty_like(x), torch.empty_like(x))
+    _same(x, ec, eu, eps, x0, what="dmc_cfg_x0")
     _steps(N, x.device, t, what="dmc_cfg_x0")
-    eps = torch.empty_like(x)
-    x0 = torch.empty_like(x)
     p = float(p_threshold) if p_threshold is not None else -1.0
     check(LIB.dmc_cfg_x0(ptr(x), ptr(ec), ptr(eu), float(scale), ptr(t), ptr(ta), ptr(tb), int(mode), N,
                          x.numel() // N, p, ptr(eps), ptr(x0), L.stream()), "dmc_cfg_x0")
