@@ -273,6 +273,76 @@ __global__ void ddpm_step_kernel(const float* x, const float* eps, const float* 
   }
 }
 
+// DPM-Solver++ multistep update in data-prediction form (diffusion/_dpm.py builds the coefficient rows on the host,
+// so nothing here is transcendental). One element: x0 from eps (or given), optional clamp, the order-1 terms, and the
+// history term only where the row has one; every op is a separate rounding.
+struct DpmRow {
+  float sa, s1, cx, c0, c1;
+};
+
+DMC_DEV void dpm_elem(const DpmRow& r, bool from_eps, int clip, float x, float e, float x0, float xp, float& o,
+                      float& x0o) {
+  if (from_eps) {
+    const float num = x - r.s1 * e;
+    x0 = num / r.sa;
+  }
+  if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+  const float u = r.cx * x;
+  const float v = r.c0 * x0;
+  float y = u + v;
+  if (r.c1 != 0.f) y = y + r.c1 * xp;
+  o = y;
+  x0o = x0;
+}
+
+// blockIdx.y strides over samples, blockIdx.x over the sample's elements: the row index and the five coefficients
+// are block-uniform, read once per sample. VEC: 16-byte accesses (per % 4 == 0 and every pointer 16-byte aligned).
+// x0_out may alias x0_prev: an element's history is read before the same thread writes that element.
+template <bool VEC>
+__global__ __launch_bounds__(256) void dpm_step_kernel(const float* x, const float* eps, const float* x0_in,
+                                                       const float* x0_prev, const int64_t* step, const float* coef,
+                                                       int S, int N, int per, int clip, float* out, float* x0_out) {
+  const bool from_eps = x0_in == nullptr;
+  for (int n = blockIdx.y; n < N; n += gridDim.y) {
+    long s = step[n];
+    s = s < 0 ? 0 : (s > S - 1 ? S - 1 : s);   // never index past the table
+    const float* c = coef + s * 5;
+    const DpmRow r{c[0], c[1], c[2], c[3], c[4]};
+    const bool hist = r.c1 != 0.f && x0_prev != nullptr;
+    const float nohist = r.c1 != 0.f ? NAN : 0.f;   // an order-2 row without a history buffer: NaN out, no fault
+    const size_t base = (size_t)n * per;
+    if (VEC) {
+      const int per4 = per / 4;
+      for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < per4; q += gridDim.x * blockDim.x) {
+        const size_t i = base + (size_t)q * 4;
+        const v4f xv = *(const v4f*)(x + i);
+        v4f ev = {0.f, 0.f, 0.f, 0.f}, x0v = ev, pv = {nohist, nohist, nohist, nohist}, ov, x0ov;
+        if (from_eps) ev = *(const v4f*)(eps + i);
+        else x0v = *(const v4f*)(x0_in + i);
+        if (hist) pv = *(const v4f*)(x0_prev + i);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          float o, x0o;
+          dpm_elem(r, from_eps, clip, xv[k], ev[k], x0v[k], pv[k], o, x0o);
+          ov[k] = o;
+          x0ov[k] = x0o;
+        }
+        *(v4f*)(out + i) = ov;
+        *(v4f*)(x0_out + i) = x0ov;
+      }
+    } else {
+      for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < per; q += gridDim.x * blockDim.x) {
+        const size_t i = base + q;
+        float o, x0o;
+        dpm_elem(r, from_eps, clip, x[i], from_eps ? eps[i] : 0.f, from_eps ? 0.f : x0_in[i],
+                 hist ? x0_prev[i] : nohist, o, x0o);
+        out[i] = o;
+        x0_out[i] = x0o;
+      }
+    }
+  }
+}
+
 // One block per sample: CFG combine, x0 prediction, optional dynamic threshold (torch.quantile, linear).
 __global__ __launch_bounds__(1024) void cfg_x0_kernel(const float* x, const float* ec, const float* eu, float scale,
                                                       const int64_t* t, const float* ta, const float* tb, int mode,
@@ -622,6 +692,24 @@ extern "C" int dmc_ddpm_step(const float* x, const float* eps, const float* x0_i
   ddpm_step_kernel<<<grid_for((long)N * per), 256, 0, dmc::as_stream(stream)>>>(x, eps, x0_in, t, sra, srm1, c1, c2, lv,
                                                                                  N, per, clip, z, out);
   return dmc::check_launch("dmc_ddpm_step");
+}
+
+extern "C" int dmc_dpm_step(const float* x, const float* eps, const float* x0_in, const float* x0_prev,
+                            const int64_t* step, const float* coef, int S, int N, int per, int clip, float* out,
+                            float* x0_out, void* stream) {
+  DMC_REQUIRE(S > 0 && N > 0 && per > 0, "dpm_step: S %d, N %d, per_sample %d must be positive", S, N, per);
+  DMC_REQUIRE(x && step && coef && out && x0_out, "dpm_step: x, step, coef, out and x0_out must not be NULL");
+  DMC_REQUIRE(eps || x0_in, "dpm_step: eps may be NULL only when x0_in is given");
+  const uintptr_t bits = (uintptr_t)x | (uintptr_t)eps | (uintptr_t)x0_in | (uintptr_t)x0_prev | (uintptr_t)out |
+                         (uintptr_t)x0_out;   // a NULL operand adds no bits
+  const bool vec = per % 4 == 0 && (bits & 15) == 0;
+  const int gx = grid_for(vec ? per / 4 : per);
+  const int gy_cap = 16384 / gx > 0 ? 16384 / gx : 1;
+  const dim3 grid(gx, N < gy_cap ? N : gy_cap);
+  hipStream_t s = dmc::as_stream(stream);
+  if (vec) dpm_step_kernel<true><<<grid, 256, 0, s>>>(x, eps, x0_in, x0_prev, step, coef, S, N, per, clip, out, x0_out);
+  else dpm_step_kernel<false><<<grid, 256, 0, s>>>(x, eps, x0_in, x0_prev, step, coef, S, N, per, clip, out, x0_out);
+  return dmc::check_launch("dmc_dpm_step");
 }
 
 extern "C" int dmc_cfg_x0(const float* x, const float* ec, const float* eu, float scale, const int64_t* t,

@@ -1,0 +1,155 @@
+"""DPM-Solver++ sampler (Lu et al. 2022, arXiv:2211.01095): multistep, data-prediction form, orders 1 and 2 (2M).
+
+Not in the reference, whose samplers are DDPM (1000 evaluations) and DDIM (50). A second-order multistep solver on
+a log-SNR grid reaches DDIM-50's discretisation error in about 20 evaluations. The class carries the same tables,
+attributes and training methods as DDIM, so it can stand in as a DiffusionTrainer's `diffusion` object.
+
+Host side (diffusion/_dpm.py): the inference timesteps and one [S', 5] fp32 coefficient row per step, computed in
+float64 from the fp32 alphas_cumprod table. Device side: ONE fused kernel per step (dmc_dpm_step: x0 prediction,
+clamp, update, history write). The loop state is a [2, B, C, H, W] tensor, x and the previous x0 prediction: it is
+the step function's first input and its output, so the history rides through graph replays (diffusion/_graph.py)
+and a cached graph that replays from step 0 starts from the caller's fresh state. Row 0 has c1 = 0 and never reads
+the history, so the same captured step serves every i. CFG reuses dmc_cfg_x0 (guided eps, x0, dynamic threshold)
+unchanged and hands its x0 to dmc_dpm_step.
+"""
+import os
+
+import torch
+from tqdm import tqdm
+
+from .. import kernels as K
+from . import _dpm
+from ._graph import StepGraph, cache_for, run_loop
+from .ddim import DDIM
+from .ddpm import DDPM, _require_cuda
+
+
+class DPMSolver(DDIM):
+    """DPM-Solver++ with DDIM's tables, q_sample / p_losses / _extract and sampling entry points."""
+
+    def __init__(self, num_timesteps=1000, num_inference_steps=20, beta_start=0.0001, beta_end=0.02,
+                 beta_schedule='linear', solver_order=2, timestep_spacing='logsnr', lower_order_final=True,
+                 device='cuda'):
+        if solver_order not in (1, 2):
+            raise ValueError(f"solver_order must be 1 or 2, got {solver_order}")
+        if timestep_spacing not in _dpm.SPACINGS:
+            raise ValueError(f"Unknown timestep spacing: {timestep_spacing} (expected one of {_dpm.SPACINGS})")
+        self.solver_order = solver_order
+        self.timestep_spacing = timestep_spacing
+        self.lower_order_final = bool(lower_order_final)
+        super().__init__(num_timesteps, num_inference_steps, beta_start, beta_end, beta_schedule, eta=0.0,
+                         device=device)
+
+    def _setup_inference_timesteps(self):
+        """num_inference_steps keeps the request; with 'logsnr' len(inference_timesteps) can be below it."""
+        ac = self.alphas_cumprod.cpu().numpy()
+        ts = _dpm.dpm_timesteps(self.num_timesteps, self.num_inference_steps, self.timestep_spacing, ac)
+        coef = _dpm.dpm_coefficients(ac, ts, self.solver_order, self.lower_order_final)
+        self.inference_timesteps = torch.from_numpy(ts).to(self.device)
+        self.step_coefficients = torch.from_numpy(coef).to(self.device)
+
+    def p_sample(self, *args, **kwargs):
+        raise NotImplementedError("DPMSolver is a multistep solver: a step needs the previous x0 prediction; use "
+                                  "sample / sample_with_cfg (kernels.dpm_step is the single update)")
+
+    def _step_tables(self, batch_size, dev):
+        """([S', B] timesteps, [S', B] row indices into the coefficient table), int64 on dev."""
+        ts = self.inference_timesteps.to(dev)
+        S = ts.shape[0]
+        tab = ts.view(-1, 1).expand(-1, batch_size).contiguous()
+        idx = torch.arange(S, dtype=torch.long, device=dev).view(-1, 1).expand(-1, batch_size).contiguous()
+        return tab, idx
+
+    @staticmethod
+    def _state(img):
+        """[2, B, C, H, W]: x_T and an (unread) zero history."""
+        st = torch.zeros((2,) + tuple(img.shape), dtype=torch.float32, device=img.device)
+        st[0].copy_(img)
+        return st
+
+    def _key(self, tag, coef, *rest):
+        return (tag, self.solver_order, self.timestep_spacing, self.lower_order_final, coef.shape[0],
+                coef.data_ptr()) + rest
+
+    def _run(self, model, st, S, inputs, fn, return_all_timesteps, key, const, desc):
+        imgs = []
+        bar = tqdm(total=S, desc=desc)
+
+        def record(i, s):
+            bar.update(1)
+            if return_all_timesteps:
+                imgs.append(s[0].cpu())
+
+        cache = None if return_all_timesteps else cache_for(model, key, self, st)
+        st = run_loop(st, S, inputs, fn, StepGraph.eligible(model, st[0], True, False), record, cache=cache,
+                      const=const)
+        bar.close()
+        if return_all_timesteps:
+            return torch.stack(imgs, dim=0)
+        return st[0]
+
+    @torch.no_grad()
+    def sample(self, model, shape, y=None, return_all_timesteps=False, x_T=None, clip_denoised=True):
+        """S' model evaluations, S' = len(inference_timesteps); the last one returns its x0 prediction."""
+        batch_size = shape[0]
+        img = torch.randn(shape, device=self.device) if x_T is None else x_T.to(self.device).float()
+        _require_cuda(img)
+        dev = img.device
+        tab, idx = self._step_tables(batch_size, dev)
+        coef = self._tab("step_coefficients", dev)
+        S = coef.shape[0]
+        if y is not None:
+            y = y.to(dev)
+        has_y = y is not None
+        clip = bool(clip_denoised)
+        # as DDIM.sample: a model that takes a length-1 t runs its time-embedding MLPs once per step
+        shared_t = (y is None and getattr(model, "shared_timestep", False)
+                    and os.environ.get("DMC_SHARED_T", "1") != "0")
+
+        def inputs(i, st):
+            return (st, tab[i], idx[i]) + ((y,) if has_y else ())
+
+        def fn(st, t, k, yy=None):
+            x = st[0]
+            eps = model(x, t[:1] if shared_t else t, yy)
+            new = torch.empty_like(st)
+            K.dpm_step(x, eps.contiguous().float(), k, coef, clip=clip, x0_prev=st[1], out=new[0], x0_out=new[1])
+            return new
+
+        key = self._key("dpm", coef, clip, shared_t, has_y, self.alphas_cumprod.data_ptr())
+        return self._run(model, self._state(img), S, inputs, fn, return_all_timesteps, key,
+                         (3,) if has_y else (), 'DPM-Solver++ Sampling')
+
+    @torch.no_grad()
+    def sample_with_cfg(self, model, shape, y, cfg_scale=3.0, p_threshold=0.995, return_all_timesteps=False,
+                        x_T=None):
+        """Classifier-free guidance + dynamic thresholding as DDIM.sample_with_cfg: one 2B forward, dmc_cfg_x0 for the
+        guided, thresholded x0, then the solver update from that x0."""
+        if y is None:
+            raise ValueError("CFG sampling requires class labels y.")
+        if p_threshold is not None and not (0.0 < float(p_threshold) < 1.0):
+            raise ValueError("p_threshold must be in (0, 1) or None")
+        batch_size = shape[0]
+        img = torch.randn(shape, device=self.device) if x_T is None else x_T.to(self.device).float()
+        _require_cuda(img)
+        dev = img.device
+        y = y.to(dev)
+        tab, idx = self._step_tables(batch_size, dev)
+        coef = self._tab("step_coefficients", dev)
+        ac = self._tab("alphas_cumprod", dev)
+        S = coef.shape[0]
+
+        def inputs(i, st):
+            return (st, tab[i], idx[i], y)
+
+        def fn(st, t, k, yy):
+            x = st[0]
+            eps_c, eps_u = DDPM._cfg_eps(model, x, t, yy)
+            _, x0 = K.cfg_x0(x, eps_c.contiguous(), eps_u.contiguous(), cfg_scale, t, ac, None, 0, p_threshold)
+            new = torch.empty_like(st)
+            K.dpm_step(x, None, k, coef, clip=False, x0=x0, x0_prev=st[1], out=new[0], x0_out=new[1])
+            return new
+
+        key = self._key("dpm_cfg", coef, float(cfg_scale), p_threshold, ac.data_ptr())
+        return self._run(model, self._state(img), S, inputs, fn, return_all_timesteps, key, (3,),
+                         f"DPM-Solver++ sampling with CFG scale {cfg_scale}")

@@ -532,6 +532,32 @@ def ddpm_step(x, eps, t, sra, srm1, c1, c2, logvar, clip=True, x0=None, z=None, 
     return out
 
 
+def dpm_step(x, eps, step, coef, clip=True, x0=None, x0_prev=None, out=None, x0_out=None):
+    """DPM-Solver++ update (dmc_dpm_step): step[n] picks sample n's row of the [S, 5] coefficient table
+    (diffusion/_dpm.py). eps may be None when x0 is given; x0_out may be x0_prev. Returns (out, x0_out)."""
+    if out is None:
+        out = torch.empty_like(x)
+    if x0_out is None:
+        x0_out = torch.empty_like(x)
+    N = x.shape[0]
+    if eps is None and x0 is None:
+        raise L.DMCError("dmc_dpm_step: eps may be None only when x0 is given")
+    _same(x, eps, x0, x0_prev, out, x0_out, what="dmc_dpm_step")
+    _steps(N, x.device, step, what="dmc_dpm_step")
+    if step is None or N < 1 or x.numel() < 1:
+        raise L.DMCError(f"dmc_dpm_step: needs a step index and a non-empty batch, got shape {tuple(x.shape)}")
+    for t in (x, eps, x0, x0_prev, out, x0_out):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise L.DMCError(f"dmc_dpm_step: operands must be contiguous fp32, got {t.dtype} strides {t.stride()}")
+    if (coef.dim() != 2 or coef.shape[1] != 5 or coef.shape[0] < 1 or coef.dtype != torch.float32
+            or coef.device != x.device or not coef.is_contiguous()):
+        raise L.DMCError(f"dmc_dpm_step: coef must be a contiguous fp32 [S, 5] tensor on {x.device}, got "
+                         f"{coef.dtype} {tuple(coef.shape)} on {coef.device}")
+    check(LIB.dmc_dpm_step(ptr(x), ptr(eps), ptr(x0), ptr(x0_prev), ptr(step), ptr(coef), coef.shape[0], N,
+                           x.numel() // N, int(clip), ptr(out), ptr(x0_out), L.stream()), "dmc_dpm_step")
+    return out, x0_out
+
+
 def cfg_x0(x, ec, eu, scale, t, ta, tb, mode, p_threshold, out=None):
     """(eps, x0) of the guided step; out: the two buffers to fill (allocated if None)."""
     N = x.shape[0]

@@ -292,6 +292,18 @@ int dmc_ddpm_step(const float* x, const float* eps, const float* x0_in, const in
                   const float* sqrt_recip_ac, const float* sqrt_recipm1_ac, const float* coef1,
                   const float* coef2, const float* logvar, int N, int per_sample, int clip,
                   const float* z, float* out, void* stream);
+/* DPM-Solver++ multistep update in data-prediction form, orders 1 and 2.
+ * coef: [S][5] fp32 rows {sa, s1, cx, c0, c1}; step[n] in [0,S) picks sample n's row (an index
+ * outside is clamped into the table).
+ *   x0  = x0_in ? x0_in[i] : (x[i] - s1*eps[i]) / sa;   if (clip) x0 = clamp(x0, -1, 1)
+ *   out = (cx*x[i] + c0*x0) + (c1 != 0 ? c1*x0_prev[i] : nothing)   -- each op rounded once, no fma
+ *   x0_out[i] = x0                                    -- x0_out may be the same buffer as x0_prev
+ * A row with c1 == 0 never reads x0_prev (it may be NULL or hold NaN); a row with c1 != 0 and
+ * x0_prev == NULL gives NaN. eps may be NULL when x0_in is given. 16-byte accesses when
+ * per_sample % 4 == 0 and every pointer is 16-byte aligned, element-wise otherwise. */
+int dmc_dpm_step(const float* x, const float* eps, const float* x0_in, const float* x0_prev,
+                 const int64_t* step, const float* coef, int S, int N, int per_sample, int clip,
+                 float* out, float* x0_out, void* stream);
 /* CFG + x0 prediction + dynamic threshold (diffusion/ddim.py:300-325, ddpm.py:284-303):
  * eps = eu + s*(ec - eu) -> eps_out; x0 = mode 0: (x - sqrt(1-a)eps)/sqrt(a) [DDIM]
  * mode 1: sra*x - srm1*eps [DDPM]; threshold: p in (0,1): per-row quantile of |x0| (linear
