@@ -51,6 +51,16 @@ class WgradJob(ctypes.Structure):
                 ("scale", ctypes.c_float), ("layout", ctypes.c_int)]
 
 
+class WgradGroupItem(ctypes.Structure):
+    """include/dmc.h dmc_wgrad_group_item"""
+    _fields_ = [("d", ctypes.POINTER(ConvDesc)), ("dy", ctypes.c_void_p), ("ld_dy", ctypes.c_int),
+                ("x1", ctypes.c_void_p), ("x2", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
+                ("dw", ctypes.c_void_p), ("scale", ctypes.c_float)]
+
+
+WGRAD_GROUP_MAX = 8   # include/dmc.h DMC_WGRAD_GROUP_MAX
+
+
 class ColsumJob(ctypes.Structure):
     """include/dmc.h dmc_colsum_job"""
     _fields_ = [("in_", ctypes.c_void_p), ("R", ctypes.c_int), ("C", ctypes.c_int), ("ld", ctypes.c_long),
@@ -88,6 +98,11 @@ def _load():
         "dmc_conv2d_wgrad_partial": (_c_int, [ctypes.POINTER(ConvDesc), _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_f,
                                               ctypes.POINTER(WgradJob), _c_p]),
         "dmc_wgrad_reduce_batch": (_c_int, [ctypes.POINTER(WgradJob), _c_int, _c_p]),
+        "dmc_conv2d_wgrad_group_ok": (_c_int, [ctypes.POINTER(ConvDesc), _c_int]),
+        "dmc_conv2d_wgrad_group_workspace": (_c_size, [ctypes.POINTER(WgradGroupItem), _c_int,
+                                                       ctypes.POINTER(_c_size)]),
+        "dmc_conv2d_wgrad_group": (_c_int, [ctypes.POINTER(WgradGroupItem), _c_int, ctypes.POINTER(WgradJob), _c_p]),
+        "dmc_wgrad_slab_bytes": (_c_long, [_c_int]),
         "dmc_pack_weight": (_c_int, [_c_int, _c_int, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p]),
         "dmc_pack_tiles": (_c_int, [ctypes.POINTER(PackJob), _c_int, _c_p, _c_int]),
         "dmc_pack_weights": (_c_int, [_c_p, _c_p, _c_int, _c_p]),

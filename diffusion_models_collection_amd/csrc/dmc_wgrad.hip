@@ -7,6 +7,10 @@
 //   * wgrad1x1_glds_kernel: 1x1 / Linear (dw-shaped slab);
 //   * conv_wgrad_kernel: everything else ([split][kk][co] slab);
 //   * wgrad_reduce_batch_kernel: the split reductions, up to 32 per launch (dmc_wgrad_reduce_batch).
+// The pipelined 3x3 and the 1x1 kernels take a by-value table of up to 8 jobs (dmc_conv2d_wgrad_group).
+#include <algorithm>
+#include <atomic>
+
 #include "dmc_conv_impl.h"
 
 namespace {
@@ -445,10 +449,27 @@ DMC_DEV v4i tr2(const char* pa, const char* pb) {
   return r;
 }
 
+// One launch serves up to kWgGroup convs of the same map width (dmc_conv2d_wgrad_group): the 1-D grid is the
+// concatenation of the jobs' (ci chunk, co tile, split) ranges, every block runs at most `tps` tiles of its job, and a
+// block finds its job in this by-value table (kernel arguments: the launch is captured into the step's HIP graph).
+// With the same total block count each conv gets 1 / njobs of the splits: its slab, its share of the reduction and
+// its end-of-kernel store burst shrink by njobs, and the pipeline fill is amortised over njobs times as many tiles.
+constexpr int kWgGroup = DMC_WGRAD_GROUP_MAX;
+struct WgPipeJob {
+  const char* x1; const char* x2; const char* dy;
+  float* slab;   // [splits][Cout][Ctot][9]
+  float* wgb;    // [splits][Cpad] bias partials (nullptr: off)
+  int x1_bytes, x2_bytes, dy_bytes, ld1, ld2, ld_dy;
+  int C1, C2, Cout, H, OHW, ntiles, ncb, nob, Cpad;
+};
+struct WgPipeGroup {
+  int njobs, tps;
+  int first[kWgGroup + 1];   // first block of each job (after the XCD remap)
+  WgPipeJob j[kWgGroup];
+};
+
 template <int OW>
-__global__ __launch_bounds__(512, 2) void wgrad3x3_pipe_kernel(ConvK a, const char* dy, int ld_dy, int dy_bytes,
-                                                             float* slab, int tiles_per_split, int ncb, int nob,
-                                                             int Cpad) {
+__global__ __launch_bounds__(512, 2) void wgrad3x3_pipe_kernel(WgPipeGroup grp) {
   using T = bf16_t;
   using G = WgPipeGeo<OW>;
   constexpr int HPW = G::HPW, HB = G::HB, SPT = G::SPT, TILE = G::TILE;
@@ -466,10 +487,22 @@ __global__ __launch_bounds__(512, 2) void wgrad3x3_pipe_kernel(ConvK a, const ch
   // dy slice (same co tile and split) or an x slice (same ci chunk and split) read it through one L2
   const int nblk = (int)gridDim.x, per8 = nblk >> 3, bid = (int)blockIdx.x;
   const int lin = bid < (per8 << 3) ? (bid & 7) * per8 + (bid >> 3) : bid;
-  const int zb = lin / (ncb * nob), rem = lin - zb * ncb * nob;
+  // the remap is a bijection of [0, nblk) for any nblk (blocks past the last multiple of 8 keep their index), and the
+  // job is looked up after it: a job boundary may fall anywhere inside an XCD's range
+  // (branch-free over the whole table, then one copy of the job: two batches of kernel-argument loads, not a chain
+  // of dependent ones)
+  int jb = 0;
+#pragma unroll
+  for (int i = 1; i < kWgGroup; ++i) jb += (i < grp.njobs && lin >= grp.first[i]) ? 1 : 0;
+  const WgPipeJob a = grp.j[jb];
+  const int loc = lin - grp.first[jb];
+  const int ncb = a.ncb, nob = a.nob, tiles_per_split = grp.tps, ld_dy = a.ld_dy, dy_bytes = a.dy_bytes, Cpad = a.Cpad;
+  const char* const dy = a.dy;
+  float* const slab = a.slab;
+  const int zb = loc / (ncb * nob), rem = loc - zb * ncb * nob;
   const int cob = rem / ncb, cib = rem - cob * ncb;
   const int c0 = cib * 64, co0 = cob * 64;
-  const int ntiles = a.M / TILE;
+  const int ntiles = a.ntiles;
   // the split's tiles: the first half of them to half 0, the rest to half 1 (both run nt stages pairs: the barriers
   // are the block's; a half with fewer tiles idles through the last pair)
   const int s_begin = zb * tiles_per_split, s_end = min(ntiles, s_begin + tiles_per_split);
@@ -685,10 +718,24 @@ __global__ __launch_bounds__(512, 2) void wgrad3x3_pipe_kernel(ConvK a, const ch
 // straight into LDS (buffer_load ... lds; no register staging, no ds_write), 32-byte segments XOR-swizzled on the
 // source column (the dy image of wgrad3x3_halo_kernel), read transposed (ds_read_b64_tr_b16). STAGES-deep ring,
 // one barrier per stage. Requires M % SPX == 0 and whole-stage split ranges (the planner checks).
+// One launch serves up to kWgGroup layers (dmc_conv2d_wgrad_group, like wgrad3x3_pipe_kernel): the 1-D grid is the
+// concatenation of the jobs' (ci tile, co tile, split) ranges with one shared pixels-per-split, the job table is a
+// kernel argument.
+struct Wg1x1Job {
+  const char* x1; const char* x2; const char* dy;
+  float* slab;   // [splits][Cout][Ctot]
+  float* wgb;    // [splits][nco * 128] bias partials (nullptr: off)
+  int x1_bytes, x2_bytes, dy_bytes, ld1, ld2, ld_dy;
+  int C1, C2, Cout, M, nci, nco;
+};
+struct Wg1x1Group {
+  int njobs, pps, xcd;
+  int first[kWgGroup + 1];   // first block of each job (after the XCD remap)
+  Wg1x1Job j[kWgGroup];
+};
+
 template <int SPX, int STAGES>
-__global__ __launch_bounds__(256) void wgrad1x1_glds_kernel(ConvK a, const char* dy, int ld_dy, int dy_bytes,
-                                                            float* slab, int KK, int pix_per_split, int nci, int nco,
-                                                            int xcd) {
+__global__ __launch_bounds__(256) void wgrad1x1_glds_kernel(Wg1x1Group grp) {
   using T = bf16_t;
   constexpr int OPB = SPX * 256;           // bytes per operand per stage (SPX rows of 128 bf16 channels)
   constexpr int SB = 2 * OPB;              // stage: dy image then x image
@@ -704,7 +751,15 @@ __global__ __launch_bounds__(256) void wgrad1x1_glds_kernel(ConvK a, const char*
   // so block b takes tile (b mod 8) * (n / 8) + b / 8 -- each XCD works on a contiguous tile range, and the blocks
   // that share a dy slice (same co tile and split) or an x slice (same ci tile and split) read it through one L2
   const int bid = blockIdx.x, per8 = (int)(gridDim.x >> 3);
-  const int t = (xcd && bid < (per8 << 3)) ? (bid & 7) * per8 + (bid >> 3) : bid;
+  const int lin = (grp.xcd && bid < (per8 << 3)) ? (bid & 7) * per8 + (bid >> 3) : bid;
+  int jb = 0;   // branch-free lookup, one copy of the job (two batches of kernel-argument loads)
+#pragma unroll
+  for (int i = 1; i < kWgGroup; ++i) jb += (i < grp.njobs && lin >= grp.first[i]) ? 1 : 0;
+  const Wg1x1Job a = grp.j[jb];
+  const int t = lin - grp.first[jb];
+  const int nci = a.nci, nco = a.nco, pix_per_split = grp.pps, ld_dy = a.ld_dy, dy_bytes = a.dy_bytes;
+  const char* const dy = a.dy;
+  float* const slab = a.slab;
   const int zb = t / (nci * nco), rem = t - zb * nci * nco;
   const int cob = rem / nci, cib = rem - cob * nci;
   const int ci0 = cib * 128, co0 = cob * 128;
@@ -1274,7 +1329,210 @@ WgPipePlan wgrad_pipe_plan(const dmc_conv_desc* d, int ld_dy) {
   return p;
 }
 
+WgPipeJob wg_pipe_job(const ConvK& k, const dmc_conv_desc* d, const void* dy, int ld_dy, float* slab, float* wgb) {
+  WgPipeJob j;
+  j.x1 = k.x1; j.x2 = k.x2; j.dy = (const char*)dy;
+  j.slab = slab; j.wgb = wgb;
+  j.x1_bytes = k.x1_bytes; j.x2_bytes = k.x2_bytes; j.dy_bytes = (int)((size_t)k.M * ld_dy * 2);
+  j.ld1 = k.ld1; j.ld2 = k.ld2; j.ld_dy = ld_dy;
+  j.C1 = k.C1; j.C2 = k.C2; j.Cout = k.Cout; j.H = k.H; j.OHW = k.OHW;
+  j.ntiles = k.M / (k.OW == 4 ? 64 : 128);
+  j.ncb = d->Kc / 64; j.nob = dmc::cdiv(d->Cout, 64);
+  j.Cpad = dmc::cdiv(d->Cout, 128) * 128;
+  return j;
+}
+
+// wgrad1x1_glds_kernel applies: 1x1 stride-1 bf16 (Linear-shaped), whole 64-pixel stages, 8-aligned channels and
+// pitches, a second source only behind a 128-aligned first one, 32-bit buffer offsets
+bool wg1x1_ok(const dmc_conv_desc* d, const ConvK& k, int ld_dy) {
+  const bool direct = d->ntaps == 1 && k.stride == 1 && k.mode == DMC_MODE_NORMAL && k.tdy0 == 0 && k.tdx0 == 0 &&
+                      k.H == k.OH && k.W == k.OW && k.prologue == DMC_PRO_NONE;
+  return d->dtype == DMC_BF16 && direct && k.M % 64 == 0 && d->Cout % 8 == 0 && ld_dy % 8 == 0 && k.C1 % 8 == 0 &&
+         k.C2 % 8 == 0 && (k.C2 == 0 || k.C1 % 128 == 0) && k.ld1 % 8 == 0 && (k.C2 == 0 || k.ld2 % 8 == 0) &&
+         k.x1_bytes > 0 && (k.C2 == 0 || k.x2_bytes > 0) && (size_t)k.M * ld_dy * 2 < 0x7fff0000u;
+}
+
+// Pixels per split of a single 1x1 layer: one round of blocks (two per CU: <= 512, e.g. 504 not 516 for the 16x16
+// qkv's 12 tiles -- a 4-block second round cost 24 %) and >= 256 pixels per block (fewer, longer splits on the 8x8 /
+// 4x4 maps): the block-count sweep's per-shape optimum within ~4 % (scripts/wgrad_sweep.py --only 1x1, round 5);
+// whole 64-pixel stages, never more splits than wgrad_splits() counted (the workspace query's bound)
+int wg1x1_single_pps(const dmc_conv_desc* d) {
+  int pps;
+  const int ws_splits = wgrad_splits(d, &pps);
+  const int M = d->N * d->OH * d->OW;
+  const long tiles = (long)dmc::cdiv(d->Kc, 128) * dmc::cdiv(d->Cout, 128);
+  long sp = std::min(512 / tiles, (long)M / 256);
+  if (sp > ws_splits) sp = ws_splits;
+  if (sp < 1) sp = 1;
+  return dmc::cdiv(dmc::cdiv(M, (int)sp), 64) * 64;
+}
+
+Wg1x1Job wg1x1_job(const ConvK& k, const dmc_conv_desc* d, const void* dy, int ld_dy, float* slab, float* wgb) {
+  Wg1x1Job j;
+  j.x1 = k.x1; j.x2 = k.x2; j.dy = (const char*)dy;
+  j.slab = slab; j.wgb = wgb;
+  j.x1_bytes = k.x1_bytes; j.x2_bytes = k.x2_bytes; j.dy_bytes = (int)((size_t)k.M * ld_dy * 2);
+  j.ld1 = k.ld1; j.ld2 = k.ld2; j.ld_dy = ld_dy;
+  j.C1 = k.C1; j.C2 = k.C2; j.Cout = k.Cout; j.M = k.M;
+  j.nci = dmc::cdiv(d->Kc, 128); j.nco = dmc::cdiv(d->Cout, 128);
+  return j;
+}
+
+void wg_pipe_launch(int ow, const WgPipeGroup& grp, hipStream_t s) {
+  const dim3 g1(grp.first[grp.njobs]);
+  if (ow == 32) wgrad3x3_pipe_kernel<32><<<g1, 512, 0, s>>>(grp);
+  else if (ow == 16) wgrad3x3_pipe_kernel<16><<<g1, 512, 0, s>>>(grp);
+  else if (ow == 8) wgrad3x3_pipe_kernel<8><<<g1, 512, 0, s>>>(grp);
+  else wgrad3x3_pipe_kernel<4><<<g1, 512, 0, s>>>(grp);
+}
+
+// Plan of a grouped launch sequence (dmc_conv2d_wgrad_group): consecutive jobs share a launch while their output tiles
+// (base = ci chunks x co tiles) stay within a quarter of the one-round block target, and a launch's jobs share one
+// tiles-per-split: the smallest for which sum_j base_j * ceil(ntiles_j / tps) stays within the target (of one job:
+// wgrad_pipe_plan's).
+// The 1x1 kind (wgrad1x1_glds_kernel) is planned the same way in its own units: 128 x 128 output tiles, one shared
+// pixels-per-split (whole 64-pixel stages, >= 256 pixels as in the single-layer plan), a block target of 512.
+constexpr int kWgKind1x1 = 1;
+struct WgGroupPlan {
+  int ow;                       // map width of the 3x3 kind, kWgKind1x1, or 0: not a group (a job is not eligible,
+                                // or the kinds / map widths differ)
+  int nlaunch;
+  int lfirst[kWgGroup + 1];     // launch l runs jobs [lfirst[l], lfirst[l + 1])
+  int tps[kWgGroup];            // per launch: tiles per split (3x3) / pixels per split (1x1)
+  int splits[kWgGroup];         // per job
+};
+// 32 / 16 / 8: the pipelined 3x3 kernel on that map width; kWgKind1x1; 0: not eligible
+int wg_group_kind(const dmc_conv_desc* d, int ld_dy) {
+  if (d->ntaps == 1) {
+    ConvK k;
+    if (d->dtype != DMC_BF16 || fill_convk(d, nullptr, nullptr, nullptr, nullptr, nullptr, k)) return 0;
+    return wg1x1_ok(d, k, ld_dy) ? kWgKind1x1 : 0;
+  }
+  const int ow = wgrad_pipe_plan(d, ld_dy).ow;
+  return ow == 32 || ow == 16 || ow == 8 ? ow : 0;
+}
+WgGroupPlan wg_group_plan(const dmc_wgrad_group_item* it, int n) {
+  WgGroupPlan p{};
+  long base[kWgGroup];
+  int ntiles[kWgGroup];
+  for (int i = 0; i < n; ++i) {
+    const dmc_conv_desc* d = it[i].d;
+    const int kind = wg_group_kind(d, it[i].ld_dy);
+    if (!kind || (i && kind != p.ow)) { p.ow = 0; return p; }
+    p.ow = kind;
+    if (kind == kWgKind1x1) {
+      base[i] = (long)dmc::cdiv(d->Kc, 128) * dmc::cdiv(d->Cout, 128);
+      ntiles[i] = d->N * d->OH * d->OW / 64;   // 64-pixel stages
+    } else {
+      base[i] = (long)(d->Kc / 64) * dmc::cdiv(d->Cout, 64);
+      ntiles[i] = d->N * d->OH * d->OW / 128;
+    }
+  }
+  const bool k1 = p.ow == kWgKind1x1;
+  const long target = k1 ? 512 : dmc::opt(dmc::OPT_WG_HALO_TARGET);
+  int i = 0;
+  while (i < n) {
+    int e = i + 1;
+    long sum = base[i];
+    // at most target / 4 output tiles per launch: with one tiles-per-split the launch runs sum x floor(target / sum)
+    // blocks, and every job is split at least 4 times, so >= 80 % of the block target is used (four decoder jobs of
+    // 16 + 32 + 16 + 32 tiles would run 96 x 2 = 192 blocks of 256: measured slower than ungrouped)
+    const long cap = std::max(target / 4, 1L);
+    while (e < n && sum + base[e] <= cap) sum += base[e++];
+    int maxt = 1;
+    for (int j = i; j < e; ++j) maxt = std::max(maxt, ntiles[j]);
+    int tps = k1 ? std::min(4, maxt) : 1;   // 1x1: at least 256 pixels per split
+    for (; tps < maxt; ++tps) {
+      long blocks = 0;
+      for (int j = i; j < e; ++j) blocks += base[j] * dmc::cdiv(ntiles[j], tps);
+      if (blocks <= target) break;
+    }
+    // a 1x1 launch of one job: the single-layer plan, so that it is bitwise dmc_conv2d_wgrad_partial (for 3x3 the
+    // search above already is wgrad_pipe_plan's)
+    if (k1 && e == i + 1) tps = wg1x1_single_pps(it[i].d) / 64;
+    for (int j = i; j < e; ++j) p.splits[j] = dmc::cdiv(ntiles[j], tps);
+    p.tps[p.nlaunch] = k1 ? tps * 64 : tps;
+    p.lfirst[p.nlaunch++] = i;
+    i = e;
+  }
+  p.lfirst[p.nlaunch] = n;
+  return p;
+}
+// bytes of job i's workspace: the dw-shaped slab of its splits, then the bias partials [splits][Cpad]
+size_t wg_group_bytes(const dmc_conv_desc* d, int splits) {
+  const size_t Cpad = (size_t)dmc::cdiv(d->Cout, 128) * 128;
+  return (size_t)splits * ((size_t)d->Cout * (d->C1 + d->C2) * d->ntaps + Cpad) * sizeof(float);
+}
+
+std::atomic<long> g_slab_bytes{0};   // dmc_wgrad_slab_bytes
+
 }  // namespace
+
+extern "C" long dmc_wgrad_slab_bytes(int reset) {
+  return reset ? g_slab_bytes.exchange(0) : g_slab_bytes.load();
+}
+
+extern "C" int dmc_conv2d_wgrad_group_ok(const dmc_conv_desc* d, int ld_dy) { return wg_group_kind(d, ld_dy); }
+
+extern "C" size_t dmc_conv2d_wgrad_group_workspace(const dmc_wgrad_group_item* items, int njobs, size_t* bytes) {
+  if (njobs < 1 || njobs > kWgGroup || !items) return 0;
+  const WgGroupPlan p = wg_group_plan(items, njobs);
+  if (!p.ow) return 0;
+  size_t total = 0;
+  for (int i = 0; i < njobs; ++i) {
+    const size_t b = wg_group_bytes(items[i].d, p.splits[i]);
+    if (bytes) bytes[i] = b;
+    total += b;
+  }
+  return total;
+}
+
+extern "C" int dmc_conv2d_wgrad_group(const dmc_wgrad_group_item* items, int njobs, dmc_wgrad_job* jobs, void* stream) {
+  DMC_REQUIRE(items && jobs && njobs >= 1 && njobs <= kWgGroup, "wgrad_group: %d jobs (1..%d)", njobs, kWgGroup);
+  const WgGroupPlan p = wg_group_plan(items, njobs);
+  DMC_REQUIRE(p.ow != 0, "wgrad_group: every job must be a bf16 3x3 stride-1 conv of one map width (32, 16 or 8), or "
+                         "every job a bf16 1x1 stride-1 conv");
+  hipStream_t s = dmc::as_stream(stream);
+  const bool k1 = p.ow == kWgKind1x1;
+  for (int l = 0; l < p.nlaunch; ++l) {
+    WgPipeGroup grp{};
+    Wg1x1Group grp1{};
+    grp.njobs = grp1.njobs = p.lfirst[l + 1] - p.lfirst[l];
+    grp.tps = grp1.pps = p.tps[l];
+    grp1.xcd = dmc::opt(dmc::OPT_NO_XCD) ? 0 : 1;
+    int nb = 0;
+    for (int i = p.lfirst[l]; i < p.lfirst[l + 1]; ++i) {
+      const dmc_wgrad_group_item& I = items[i];
+      const dmc_conv_desc* d = I.d;
+      DMC_REQUIRE(I.dy && I.x1 && I.workspace && I.dw, "wgrad_group: job %d pointers", i);
+      ConvK k;
+      if (fill_convk(d, I.x1, I.x2, nullptr, nullptr, nullptr, k)) return 1;
+      const int splits = p.splits[i], Ctot = d->C1 + d->C2;
+      float* const slab = (float*)I.workspace;
+      float* const bslab = d->wg_bias ? slab + (size_t)splits * d->Cout * Ctot * d->ntaps : nullptr;
+      const int q = i - p.lfirst[l];
+      grp.first[q] = grp1.first[q] = nb;
+      if (k1) {
+        grp1.j[q] = wg1x1_job(k, d, I.dy, I.ld_dy, slab, bslab);
+        nb += grp1.j[q].nci * grp1.j[q].nco * splits;
+      } else {
+        grp.j[q] = wg_pipe_job(k, d, I.dy, I.ld_dy, slab, bslab);
+        nb += grp.j[q].ncb * grp.j[q].nob * splits;
+      }
+      dmc_wgrad_job& J = jobs[i];
+      J = dmc_wgrad_job{};
+      J.slab = slab; J.bslab = bslab; J.dw = I.dw; J.dbias = d->wg_bias;
+      J.splits = splits; J.KK = d->ntaps * d->Kc; J.Cpad = dmc::cdiv(d->Cout, 128) * 128; J.Cout = d->Cout;
+      J.Ctot = Ctot; J.ntaps = d->ntaps; J.Kc = d->Kc; J.scale = I.scale; J.layout = 1;
+      g_slab_bytes += (long)((size_t)splits * d->Cout * Ctot * d->ntaps * sizeof(float));
+    }
+    grp.first[grp.njobs] = grp1.first[grp.njobs] = nb;
+    if (k1) wgrad1x1_glds_kernel<64, 2><<<dim3(nb), 256, 0, s>>>(grp1);
+    else wg_pipe_launch(p.ow, grp, s);
+    if (dmc::check_launch("dmc_conv2d_wgrad_group")) return 2;
+  }
+  return 0;
+}
 
 extern "C" size_t dmc_conv2d_wgrad_workspace(const dmc_conv_desc* d) {
   int pps;
@@ -1321,23 +1579,10 @@ static int wgrad_partial(const dmc_conv_desc* d, const void* dy, int ld_dy, cons
   if (pp.ow) splits = pp.splits;
   // 1x1 stride-1 bf16 (Linear-shaped): both operands DMA'd into LDS (wgrad1x1_glds_kernel); splits are whole
   // SPX-pixel stages, never more than wgrad_splits() counted (the workspace query's bound)
-  const bool direct = d->ntaps == 1 && k.stride == 1 && k.mode == DMC_MODE_NORMAL && k.tdy0 == 0 && k.tdx0 == 0 &&
-                      k.H == k.OH && k.W == k.OW && k.prologue == DMC_PRO_NONE;
-  constexpr int spx = 64;
-  const bool w1x1 = !halo && d->dtype == DMC_BF16 && direct && k.M % spx == 0 && d->Cout % 8 == 0 &&
-                    ld_dy % 8 == 0 && k.C1 % 8 == 0 && k.C2 % 8 == 0 && (k.C2 == 0 || k.C1 % 128 == 0) &&
-                    k.ld1 % 8 == 0 && (k.C2 == 0 || k.ld2 % 8 == 0) && k.x1_bytes > 0 && (k.C2 == 0 || k.x2_bytes > 0) &&
-                    dyb < 0x7fff0000u;
+  const bool w1x1 = !halo && wg1x1_ok(d, k, ld_dy);
   int pps1 = 0;
   if (w1x1) {
-    // one round of blocks (two per CU: <= 512, e.g. 504 not 516 for the 16x16 qkv's 12 tiles -- a 4-block second
-    // round cost 24 %) and >= 256 pixels per block (fewer, longer splits on the 8x8 / 4x4 maps): the block-count
-    // sweep's per-shape optimum within ~4 % (scripts/wgrad_sweep.py --only 1x1, round 5)
-    const long tiles = (long)g.x * g.y;
-    long sp = std::min(512 / tiles, (long)k.M / 256);
-    if (sp > splits) sp = splits;   // never above the workspace query's split count
-    if (sp < 1) sp = 1;
-    pps1 = dmc::cdiv(dmc::cdiv(k.M, (int)sp), spx) * spx;
+    pps1 = wg1x1_single_pps(d);
     splits = dmc::cdiv(k.M, pps1);
   }
   const size_t Cpad = (size_t)dmc::cdiv(d->Cout, 128) * 128;
@@ -1345,21 +1590,14 @@ static int wgrad_partial(const dmc_conv_desc* d, const void* dy, int ld_dy, cons
   float* const bslab = d->wg_bias ? (float*)workspace + (size_t)splits * KK * Cpad : nullptr;
   k.wgb = bslab;
   if (pp.ow) {
-    const int ncb = d->Kc / 64, nob = dmc::cdiv(d->Cout, 64);
-    const dim3 g1(ncb * nob * splits);
-    const int Cp = (int)Cpad;
-    if (pp.ow == 32)
-      wgrad3x3_pipe_kernel<32><<<g1, 512, 0, s>>>(k, (const char*)dy, ld_dy, (int)dyb, (float*)workspace, pp.tps, ncb,
-                                                  nob, Cp);
-    else if (pp.ow == 16)
-      wgrad3x3_pipe_kernel<16><<<g1, 512, 0, s>>>(k, (const char*)dy, ld_dy, (int)dyb, (float*)workspace, pp.tps, ncb,
-                                                  nob, Cp);
-    else if (pp.ow == 8)
-      wgrad3x3_pipe_kernel<8><<<g1, 512, 0, s>>>(k, (const char*)dy, ld_dy, (int)dyb, (float*)workspace, pp.tps, ncb,
-                                                 nob, Cp);
-    else
-      wgrad3x3_pipe_kernel<4><<<g1, 512, 0, s>>>(k, (const char*)dy, ld_dy, (int)dyb, (float*)workspace, pp.tps, ncb,
-                                                 nob, Cp);
+    // a group of one job: the single-conv plan (the grouped entry's plan of one job is the same)
+    WgPipeGroup grp{};
+    grp.njobs = 1;
+    grp.tps = pp.tps;
+    grp.j[0] = wg_pipe_job(k, d, dy, ld_dy, (float*)workspace, bslab);
+    grp.first[0] = 0;
+    grp.first[1] = grp.j[0].ncb * grp.j[0].nob * splits;
+    wg_pipe_launch(pp.ow, grp, s);
     g.y = dmc::cdiv(d->Cout, 128);   // the reduce's slab pitch: Cout rounded to 128
   } else if (halo) {
     // two blocks per CU: 64-co blocks, the same split count (twice the co tiles, half the block target's share)
@@ -1371,10 +1609,14 @@ static int wgrad_partial(const dmc_conv_desc* d, const void* dy, int ld_dy, cons
     g.y = dmc::cdiv(d->Cout, 128);   // the reduce's slab pitch: Cout rounded to 128
   } else if (w1x1) {
     g.z = splits;
-    const dim3 g1(g.x * g.y * g.z);
-    const int xcd = dmc::opt(dmc::OPT_NO_XCD) ? 0 : 1;
-    wgrad1x1_glds_kernel<64, 2><<<g1, 256, 0, s>>>(k, (const char*)dy, ld_dy, (int)dyb, (float*)workspace, KK, pps1,
-                                                  (int)g.x, (int)g.y, xcd);
+    Wg1x1Group grp{};   // a group of one job
+    grp.njobs = 1;
+    grp.pps = pps1;
+    grp.xcd = dmc::opt(dmc::OPT_NO_XCD) ? 0 : 1;
+    grp.j[0] = wg1x1_job(k, d, dy, ld_dy, (float*)workspace, bslab);
+    grp.first[0] = 0;
+    grp.first[1] = (int)(g.x * g.y * g.z);
+    wgrad1x1_glds_kernel<64, 2><<<dim3(grp.first[1]), 256, 0, s>>>(grp);
   } else if (d->dtype == DMC_F32)
     conv_wgrad_kernel<float><<<g, 256, 0, s>>>(k, (const char*)dy, ld_dy, (float*)workspace, KK, pps);
   else
@@ -1393,6 +1635,8 @@ static int wgrad_partial(const dmc_conv_desc* d, const void* dy, int ld_dy, cons
   job->Kc = d->Kc;
   job->scale = scale;
   job->layout = (pp.ow || w1x1) ? 1 : 0;   // the pipelined 3x3 and the 1x1 kernels write dw-shaped slabs
+  g_slab_bytes += (long)((size_t)splits * (job->layout ? (size_t)job->Cout * job->Ctot * job->ntaps : KK * Cpad) *
+                         sizeof(float));
   return 0;
 }
 

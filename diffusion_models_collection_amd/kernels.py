@@ -162,6 +162,12 @@ def conv_halo_prologue(d):
     return bool(LIB.dmc_conv_halo_prologue(ctypes.byref(d)))
 
 
+def _byte_span(t):
+    """[first, past-the-last) device address a (possibly strided) tensor's elements occupy."""
+    n = 1 + sum((sz - 1) * st for sz, st in zip(t.shape, t.stride())) if t.numel() else 0
+    return t.data_ptr(), t.data_ptr() + n * t.element_size()
+
+
 class WgradDefer:
     """Weight-gradient reductions deferred and batched (wgrad(defer=...) -> dmc_wgrad_reduce_batch).
 
@@ -171,15 +177,26 @@ class WgradDefer:
     3 measured best of 1-8 and of flushing only at the backward's segment ends: train 10,421 vs 10,365 img/s) and
     at every gradient-segment end (end_segment). When the pending jobs outgrow the arena they are flushed early
     and a larger arena is allocated; every arena ever allocated stays referenced (a captured HIP graph keeps
-    using its addresses)."""
+    using its addresses).
+
+    The eligible 3x3 and 1x1 weight gradients are also collected into grouped launches (group_add -> wgrad_group,
+    dmc_conv2d_wgrad_group), a queue per kind: `group` jobs (DMC_WG_DEFER = N, default 4; 3x3 alone at 1, 2, 3, 4, 6
+    measured 11,637 / 11,906 / 11,926 / 11,930 / 11,678 img/s) share the block count of one conv's launch, so each
+    conv's slab is up to N times smaller. end_segment() launches what is queued before it reduces."""
 
     def __init__(self):
         import os
         self.every = int(os.environ.get("DMC_WG_FLUSH_EVERY", "3"))
+        # 3x3 weight gradients per grouped launch (dmc_conv2d_wgrad_group): the value of DMC_WG_DEFER, 1 = one launch
+        # per conv
+        self.group = max(1, min(int(os.environ.get("DMC_WG_DEFER", "4") or 1), L.WGRAD_GROUP_MAX))
         self.arenas = []
         self.buf = None
         self.off = 0
         self.jobs = []
+        self.pending = []       # 3x3 group items not launched yet: (d, dy, ld_dy, x1, x2, dw, scale, dbias)
+        self.pending_ow = 0
+        self.pending1 = []      # the same for the 1x1 kind (any map size)
 
     def alloc(self, nbytes, device):
         nbytes = (max(int(nbytes), 256) + 255) // 256 * 256
@@ -208,7 +225,51 @@ class WgradDefer:
         self.jobs = []
         self.off = 0
 
+    def group_add(self, item):
+        """Queue a weight gradient for the next grouped launch if dmc_conv2d_wgrad_group takes it (returns False
+        otherwise: the caller launches it alone). The queue holds the operand tensors, so the allocator cannot reuse
+        them; the caller must not WRITE them before launch_pending() (see holds()). The group is launched when it
+        reaches `group` jobs or a job of another map width arrives."""
+        if self.group <= 1:
+            return False
+        ow = LIB.dmc_conv2d_wgrad_group_ok(ctypes.byref(item[0]), item[2])
+        if not ow:
+            return False
+        if ow == 1:             # the 1x1 kind: a queue of its own
+            self.pending1.append(item)
+            if len(self.pending1) >= self.group:
+                items, self.pending1 = self.pending1, []
+                wgrad_group(items, defer=self)
+            return True
+        if self.pending and ow != self.pending_ow:
+            self.launch_pending()
+        self.pending.append(item)
+        self.pending_ow = ow
+        if len(self.pending) >= self.group:
+            self.launch_pending()
+        return True
+
+    def holds(self, t):
+        """True if the bytes tensor t spans overlap those of an operand of a queued, not yet launched weight gradient
+        (views at any offset into an operand included)."""
+        lo, hi = _byte_span(t)
+        for it in self.pending + self.pending1:
+            for o in (it[1], it[3], it[4]):
+                if o is not None:
+                    olo, ohi = _byte_span(o)
+                    if lo < ohi and olo < hi:
+                        return True
+        return False
+
+    def launch_pending(self):
+        for items in (self.pending, self.pending1):
+            if items:
+                batch = items[:]
+                del items[:]
+                wgrad_group(batch, defer=self)
+
     def end_segment(self):
+        self.launch_pending()
         self.flush()
 
     def reset(self):
@@ -216,7 +277,49 @@ class WgradDefer:
         raised part-way (an OOM, a capture error the caller survived) leaves jobs holding raw slab / dw pointers that
         the next backward's first flush would otherwise replay onto reused buffers."""
         self.jobs = []
+        self.pending = []
+        self.pending1 = []
         self.off = 0
+
+
+def wgrad_slab_bytes(reset=False):
+    """Bytes of split partial sums the weight-gradient launches planned since the last reset (host-side counter)."""
+    return LIB.dmc_wgrad_slab_bytes(int(reset))
+
+
+def wgrad_group(items, defer=None):
+    """dmc_conv2d_wgrad_group: the partial-sum kernels of up to 8 eligible 3x3 weight gradients of one map width, or of
+    up to 8 eligible 1x1 ones, in shared launches. items: (d, dy, ld_dy, x1, x2, dw, scale, dbias) each. With defer (a WgradDefer) the reductions
+    join its batch, else they run at once in one dmc_wgrad_reduce_batch."""
+    n = len(items)
+    arr = (L.WgradGroupItem * n)()
+    for i, (d, dy, ld_dy, x1, x2, dw, scale, dbias) in enumerate(items):
+        d.wg_bias = ptr(dbias)
+        d._keep_wgb = dbias
+        arr[i].d = ctypes.pointer(d)
+        arr[i].dy, arr[i].ld_dy, arr[i].x1, arr[i].x2 = ptr(dy), ld_dy, ptr(x1), ptr(x2)
+        arr[i].dw, arr[i].scale = ptr(dw), scale
+    sizes = (ctypes.c_size_t * n)()
+    if not LIB.dmc_conv2d_wgrad_group_workspace(arr, n, sizes):
+        raise L.DMCError("wgrad_group: the jobs are no valid group (bf16 stride-1 convs: 3x3 of one map width, or 1x1)")
+    offs, total = [], 0
+    for i in range(n):
+        offs.append(total)
+        total += (sizes[i] + 255) // 256 * 256
+    dev = items[0][1].device
+    ws = defer.alloc(total, dev) if defer is not None else SCRATCH.get(total, dev)
+    for i in range(n):
+        arr[i].workspace = ws.data_ptr() + offs[i]
+    jobs = (L.WgradJob * n)()
+    PROF.wrap("wgrad", items[0][0], lambda: check(LIB.dmc_conv2d_wgrad_group(arr, n, jobs, L.stream()),
+                                                  "dmc_conv2d_wgrad_group"))
+    if defer is not None:
+        # all of the group's jobs first, then the flush check: a flush recycles the arena the group's slabs sit in
+        defer.jobs.extend(L.WgradJob.from_buffer_copy(jobs[i]) for i in range(n))
+        if defer.every and len(defer.jobs) >= defer.every:
+            defer.flush()
+        return
+    check(LIB.dmc_wgrad_reduce_batch(jobs, n, L.stream()), "dmc_wgrad_reduce_batch")
 
 
 def wgrad(d, dy, ld_dy, x1, x2, dw, scale=1.0, dbias=None, defer=None):
@@ -225,6 +328,8 @@ def wgrad(d, dy, ld_dy, x1, x2, dw, scale=1.0, dbias=None, defer=None):
     defer's batch."""
     d.wg_bias = ptr(dbias)
     d._keep_wgb = dbias
+    if defer is not None and defer.group_add((d, dy, ld_dy, x1, x2, dw, scale, dbias)):
+        return
     nbytes = LIB.dmc_conv2d_wgrad_workspace(ctypes.byref(d))
     if defer is not None:
         ws = defer.alloc(nbytes, dy.device)

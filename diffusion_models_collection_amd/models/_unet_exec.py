@@ -47,8 +47,12 @@ _GN_PARTIALS = os.environ.get("DMC_GN_PARTIALS", "1") not in ("", "0")
 # DMC_GN_DEFER=0: one finish launch per GroupNorm)
 _GN_DEFER = os.environ.get("DMC_GN_DEFER", "1") not in ("", "0")
 # The weight-gradient slab reductions deferred to one dmc_wgrad_reduce_batch per gradient segment (A/B switch
-# DMC_WG_DEFER=0: one reduce launch after each weight-gradient kernel)
-_WG_DEFER = os.environ.get("DMC_WG_DEFER", "1") not in ("", "0")
+# DMC_WG_DEFER=0: one reduce launch after each weight-gradient kernel). The deferred path also collects the eligible
+# 3x3 and 1x1 weight gradients into grouped launches (K.WgradDefer.group_add, DMC_WG_DEFER = N jobs each, 1 = off): a queued job's
+# operands stay referenced and must not be written before its launch -- the one place the backward writes such a
+# buffer is an aliased identity-shortcut / residual gradient (_wg_before_write); a group is launched when it is full,
+# when a job of another map width arrives, before a gradient prefix is published and at the backward's end (_flush_gn)
+_WG_DEFER = os.environ.get("DMC_WG_DEFER", "4") not in ("", "0")
 # GroupNorm statistics + apply in one launch where a sample has at most this many elements (dmc_gn_stats_apply: the
 # 4x4 levels); 0 = off. A module switch for same-box A/Bs (scripts/r5_gsa.sh), not an option. 16384 (the 8x8 levels
 # too, in place of the conv-partial finalize + apply) measured neutral to slower
@@ -437,6 +441,9 @@ class UNetExecutor(ExecCore):
         if act.grad is None:
             act.grad = torch.empty_like(act.t)
             return act.grad, 0
+        # accumulated into: if an identity shortcut aliased it from its block's dout (conv2's dy), the queued weight
+        # gradients that read it are launched first
+        self._wg_before_write(act.grad)
         return act.grad, 1
 
     # =========================================================================================
@@ -841,6 +848,7 @@ class UNetExecutor(ExecCore):
                 # GroupNorm backward below, which accumulates into a.grad anyway (round 6: one HBM pass fewer)
                 short_add = dout
             else:
+                self._wg_before_write(a.grad)
                 K.add_(dt, a.grad, dout)
         # GN2 + SiLU + dropout backward -> dh1, with its pixel sums fused in: per (n, c) -> the time-embedding
         # add's gradient (daddvec slice), per c -> conv1's bias gradient
@@ -870,6 +878,14 @@ class UNetExecutor(ExecCore):
         """K.gn_bwd with its parameter column sums (dgamma / dbeta / the bias sums) deferred to one batched launch
         per gradient segment (_flush_gn) -- 25 launches of ~4.7 us per B=128 training step became one."""
         return K.gn_bwd(*a, defer=getattr(self, "_gn_defer", None), **kw)
+
+    def _wg_before_write(self, t):
+        """Launch the queued weight-gradient groups if t overlaps one of their operands in memory: a gradient
+        buffer that an identity shortcut / residual aliased (a.grad = dout) is about to be accumulated into. Every
+        in-place write of the backward into a buffer that existed before the write goes through here."""
+        wd = getattr(self, "_wg_defer", None)
+        if wd is not None and (wd.pending or wd.pending1) and wd.holds(t):
+            wd.launch_pending()
 
     def _flush_gn(self):
         if getattr(self, "_gn_defer", None):
@@ -905,12 +921,14 @@ class UNetExecutor(ExecCore):
         if a.grad is None:
             a.grad = dout
         else:
+            self._wg_before_write(a.grad)
             K.add_(dt, a.grad, dout)
         dqkv = torch.empty(N, H, W, 3 * C, dtype=dt, device=dout.device)
         K.attn_bwd(dt, qkv.t, 3 * C, o.t, do, C, lse, N, HW, heads, hd, dqkv, 3 * C)
         self._wgrad([an], dqkv, 3 * C, K.TAPS1, H, W, 3 * C, gv(ab.qkv.weight), dbias=gv(ab.qkv.bias))
         g = torch.empty(N, H, W, C, dtype=dt, device=dout.device)
         self._conv([Act(dqkv, H, W, 3 * C)], ab.qkv, K.TAPS1, H, W, C, out=g, packmode=L.PACK_DGRAD)
+        self._wg_before_write(a.grad)
         self._gn_bwd(dt, g, C, a.t, None, N, HW, C, 0, C, 0, ab.norm.num_groups, st[2], ab.norm.weight, ab.norm.bias,
                  False, None, a.grad, None, C, 0, 1, 0, gv(ab.norm.weight), gv(ab.norm.bias))
 

@@ -144,6 +144,35 @@ int dmc_conv2d_wgrad_partial(const dmc_conv_desc* d, const void* dy, int ld_dy, 
                              void* workspace, float* dw, float scale, dmc_wgrad_job* job, void* stream);
 int dmc_wgrad_reduce_batch(const dmc_wgrad_job* jobs, int njobs, void* stream);
 
+/* Grouped weight gradients: the partial-sum kernels of up to DMC_WGRAD_GROUP_MAX convs in shared launches. Every
+ * job must be one dmc_conv2d_wgrad_group_ok accepts: bf16, and either 3x3 stride 1 with the forward taps, maps 32, 16
+ * or 8 wide, 64-aligned channel sources, ld_dy % 8 == 0 (returns the map width), or 1x1 stride 1 with N*H*W % 64 == 0,
+ * 8-aligned channels and pitches and a second source only behind a 128-aligned first one (returns 1); 0 otherwise.
+ * All jobs of a call share that return value (1x1 jobs of different map sizes do);
+ * N, C1 / C2, Cout (ragged and narrow in a padded pitch included) and d->wg_bias may differ. With the block count of
+ * one conv's launch spread over the group, each conv is split 1 / njobs as often over its pixels: its slab, its share
+ * of the reduction and its store burst shrink by that factor. The summation order is fixed (bitwise reproducible), and
+ * a launch of one job (3x3 or 1x1) has the single-layer plan: bitwise dmc_conv2d_wgrad_partial of it. jobs[i] (HOST
+ * array of njobs) receives job i's reduction for dmc_wgrad_reduce_batch; items[i].workspace needs bytes[i] of dmc_conv2d_wgrad_group_workspace (which
+ * returns their sum, 0 if the items are no valid group) and must stay untouched until that reduction ran. */
+#define DMC_WGRAD_GROUP_MAX 8
+typedef struct dmc_wgrad_group_item {
+  const dmc_conv_desc* d;
+  const void* dy;
+  int ld_dy;
+  const void* x1;
+  const void* x2;
+  void* workspace;
+  float* dw;
+  float scale;
+} dmc_wgrad_group_item;
+int dmc_conv2d_wgrad_group_ok(const dmc_conv_desc* d, int ld_dy);
+size_t dmc_conv2d_wgrad_group_workspace(const dmc_wgrad_group_item* items, int njobs, size_t* bytes);
+int dmc_conv2d_wgrad_group(const dmc_wgrad_group_item* items, int njobs, dmc_wgrad_job* jobs, void* stream);
+/* Bytes of split partial sums (the fp32 weight slabs) the weight-gradient launches of this process have planned
+ * since the last reset; reset != 0 returns the count and clears it. Host-side bookkeeping, no GPU work. */
+long dmc_wgrad_slab_bytes(int reset);
+
 /* Repack an fp32 nn.Conv2d / nn.Linear weight [Cout][Cin][kh][kw] into the kernel layout:
  * FWD [Cout][t][Kc], DGRAD [Cin][t][Kc>=Cout], UPDGRAD [Cin][16][Kc] (nearest-x2 + 3x3 folded
  * into a 4x4 stride-2 kernel). Padding is zero-filled. */

@@ -23,6 +23,8 @@ def main():
     a = ap.parse_args()
     dt, dev = torch.bfloat16, "cuda"
     defer = K.WgradDefer()
+    defer.group = 1      # one launch and one slab per layer: the ungrouped job list (no queue to launch)
+    defer.every = 0      # and no reduction before the timed ones
     defer.buf = torch.empty(int(4.2e9), dtype=torch.uint8, device=dev)   # every job of the step in one arena
     keep = []
     for name, (B, H, W, C1, C2, Cout, taps, OH, OW, mode, stride, n) in SHAPES.items():
