@@ -175,6 +175,27 @@ def _load():
         "dmc_add_bcast": (_c_int, [_c_p, _c_p, _c_long, _c_long, _c_p]),
         "dmc_batch_sum": (_c_int, [_c_p, _c_long, _c_long, _c_p, _c_p]),
         "dmc_patch_dgrad": (_c_int, [_c_p, _c_int, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p]),
+        "dmc_gate_bwd_bias": (_c_int, [_c_int, _c_p, _c_p, _c_int, _c_p, _c_int, _c_int, _c_int, _c_int, _c_u32, _c_p,
+                                       _c_u32, _c_f, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p]),
+        "dmc_gelu_bwd_f32in": (_c_int, [_c_int, _c_p, _c_p, _c_long, _c_int, _c_int, _c_u32, _c_p, _c_u32, _c_f, _c_p,
+                                        _c_p]),
+        "dmc_ln_affine_mod_fwd": (_c_int, [_c_int, _c_p, _c_p, _c_int, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int,
+                                           _c_f, _c_p, _c_p, _c_u32, _c_p, _c_u32, _c_f, _c_p, _c_p, _c_int, _c_p, _c_p,
+                                           _c_p]),
+        "dmc_ln_affine_mod_bwd": (_c_int, [_c_int, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int,
+                                           _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
+        "dmc_causal_conv_silu_fwd": (_c_int, [_c_int, _c_p, _c_int, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_int,
+                                              _c_p]),
+        "dmc_causal_conv_workspace": (_c_size, [_c_int, _c_int, _c_int]),
+        "dmc_causal_conv_silu_bwd": (_c_int, [_c_int, _c_p, _c_int, _c_p, _c_int, _c_p, _c_p, _c_int, _c_int, _c_int,
+                                              _c_p, _c_int, _c_p, _c_p, _c_p, _c_p]),
+        "dmc_scan_chunk": (_c_int, []),
+        "dmc_selective_scan_workspace": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+        "dmc_selective_scan_fwd": (_c_int, [_c_int, _c_p, _c_int, _c_p, _c_int, _c_p, _c_int, _c_p, _c_p, _c_int, _c_p,
+                                            _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_int, _c_p]),
+        "dmc_selective_scan_bwd": (_c_int, [_c_int, _c_p, _c_int, _c_p, _c_int, _c_p, _c_int, _c_p, _c_int, _c_p, _c_p,
+                                            _c_int, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p,
+                                            _c_int, _c_p, _c_int, _c_p, _c_int, _c_p, _c_int, _c_int, _c_p, _c_p, _c_p]),
         "dmc_load_batch": (_c_int, [_c_p, _c_long, _c_int, _c_int, _c_int, _c_p, _c_int, _c_p, _c_u32, _c_u32, _c_long,
                                     ctypes.POINTER(_c_f), ctypes.POINTER(_c_f), _c_p, _c_p, _c_p, _c_p]),
     }

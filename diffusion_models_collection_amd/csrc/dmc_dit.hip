@@ -51,11 +51,13 @@ struct Drop {
 };
 
 // One wave per token row. x_new = x (+ gate[b] * drop(br)); optional x_out; LayerNorm over C; h = y*(1+scale)+shift.
-template <typename T>
+// AFF: the LayerNorm has an elementwise affine (the DiM's nn.LayerNorm): h = (y*gamma+beta)*(1+scale)+shift.
+template <typename T, bool AFF>
 __global__ __launch_bounds__(256) void ln_mod_fwd_kernel(const float* x, const void* br, int ld_br, const float* gate,
                                                          const float* shift, const float* scale, int ld_mod, int T_,
                                                          int C, int L, float eps, Drop drop, float* x_out, void* h,
-                                                         int ld_h, float* mean_out, float* rstd_out) {
+                                                         int ld_h, float* mean_out, float* rstd_out,
+                                                         const float* gamma, const float* beta) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= T_) return;
@@ -106,9 +108,12 @@ __global__ __launch_bounds__(256) void ln_mod_fwd_kernel(const float* x, const v
       const v4f sc = *(const v4f*)(scale + (size_t)b * ld_mod + c);
       const v4f sh = *(const v4f*)(shift + (size_t)b * ld_mod + c);
       float o[4];
+      v4f gm = {1.f, 1.f, 1.f, 1.f}, bt = {0.f, 0.f, 0.f, 0.f};
+      if (AFF) { gm = *(const v4f*)(gamma + c); bt = *(const v4f*)(beta + c); }
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float y = (v[k][e] - mean) * rstd;
+        float y = (v[k][e] - mean) * rstd;
+        if (AFF) y = y * gm[e] + bt[e];
         o[e] = y * (1.0f + sc[e]) + sh[e];
       }
       st4<T>(h, (size_t)row * ld_h + c, o);
@@ -125,10 +130,15 @@ __global__ __launch_bounds__(256) void ln_mod_fwd_kernel(const float* x, const v
 // rows in registers, then across waves in LDS): dscale = sum dh * xhat, dshift = sum dh.
 // The image's rows are split over gridDim.y blocks (so that B x splits blocks fill the chip); with more than one
 // split each block writes its channel sums to ws[b][split][2][C] and split_sum_kernel adds them in split order.
-template <typename T>
+// AFF (affine LayerNorm with weight gamma, dmc_ln_affine_mod_bwd): the gradient reaching xhat is
+// dh * (1 + scale) * gamma; the channel sums stay A = sum dh * xhat and Hs = sum dh, which ln_affine_finish_kernel turns
+// into dscale / dshift / dgamma / dbeta.
+// gamma multiplies dh in a rounded product of its own, so that the row arithmetic after it is the plain kernel's.
+template <typename T, bool AFF>
 __global__ __launch_bounds__(256) void ln_mod_bwd_kernel(const void* dh, int ld_dh, const float* x, const float* mean,
                                                          const float* rstd, const float* scale, int ld_mod, int C, int L,
-                                                         float* dx, float* dscale, float* dshift, float* ws) {
+                                                         float* dx, float* dscale, float* dshift, float* ws,
+                                                         const float* gamma) {
   __shared__ float red[4][2][512];   // [wave][dscale | dshift][channel]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b = blockIdx.x, S = gridDim.y, sp = blockIdx.y;
@@ -162,13 +172,21 @@ __global__ __launch_bounds__(256) void ln_mod_bwd_kernel(const void* dh, int ld_
     for (int k = 0; k < kMaxV; ++k) {
       const int c = (lane + 64 * k) * 4;
       if (c < C) {
-        float d[4], xv[4];
+        float d[4], xv[4], dg[4];
         ld4<T>(dh, (size_t)row * ld_dh + c, d);
         ld4<float>(x, (size_t)row * C + c, xv);
+        if constexpr (AFF) {   // gamma is re-read per row (L1-resident) rather than held in 32 more registers
+          const v4f g4 = *(const v4f*)(gamma + c);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) dg[e] = __fmul_rn(d[e], g4[e]);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) dg[e] = d[e];
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           xh[k][e] = (xv[e] - mu) * rs;
-          g[k][e] = d[e] * sc1[k][e];
+          g[k][e] = dg[e] * sc1[k][e];
           s1 += g[k][e];
           s2 += g[k][e] * xh[k][e];
           as[k][e] += d[e] * xh[k][e];
@@ -236,21 +254,26 @@ __global__ void split_sum_kernel(const float* ws, int B, int S, int C, int nout,
 
 // One block per image: dbr = dy * gate (* mask * scale) in the compute dtype; dgate = sum over the image's rows of
 // dy * drop(br).
-template <typename T>
+// BS (dmc_gate_bwd_bias): also dsum = sum over the image's rows of dy * mask, in fp32 -- the part of the gradient of a
+// bias inside the branch that does not pass through the rounded dbr rows.
+template <typename T, bool BS>
 __global__ __launch_bounds__(256) void gate_bwd_kernel(const float* dy, const void* br, int ld_br, const float* gate,
                                                        int ld_mod, int C, int L, Drop drop, void* dbr, int ld_dbr,
-                                                       float* dgate, float* ws) {
+                                                       float* dgate, float* ws, float* dsum) {
   __shared__ float red[4][512];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b = blockIdx.x, S = gridDim.y, sp = blockIdx.y;
   const int l0 = (int)((long)L * sp / S), l1 = (int)((long)L * (sp + 1) / S);
   const uint32_t seed = drop.thresh ? drop.s() : 0u;
-  float acc[kMaxV][4], gv[kMaxV][4];
+  float acc[kMaxV][4], gv[kMaxV][4], acs[BS ? kMaxV : 1][4];
 #pragma unroll
   for (int k = 0; k < kMaxV; ++k) {
     const int c = (lane + 64 * k) * 4;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) { acc[k][e] = 0.f; gv[k][e] = 0.f; }
+    for (int e = 0; e < 4; ++e) {
+      acc[k][e] = 0.f; gv[k][e] = 0.f;
+      if constexpr (BS) acs[k][e] = 0.f;
+    }
     if (c < C) {
       const v4f g = *(const v4f*)(gate + (size_t)b * ld_mod + c);
 #pragma unroll
@@ -271,6 +294,7 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const float* dy, const vo
           float m = 1.f;
           if (drop.thresh) m = drop_keep((uint64_t)row * C + c + e, seed, drop.thresh) ? drop.scale : 0.f;
           acc[k][e] += d[e] * (r[e] * m);
+          if constexpr (BS) acs[k][e] += d[e] * m;
           o[e] = d[e] * gv[k][e] * m;
         }
         st4<T>(dbr, (size_t)row * ld_dbr + c, o);
@@ -292,8 +316,35 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const float* dy, const vo
       const int c = cb + cl;
       const float v = ((red[0][cl] + red[1][cl]) + red[2][cl]) + red[3][cl];
       if (S == 1) dgate[(size_t)b * ld_mod + c] = v;
-      else ws[(size_t)(b * S + sp) * C + c] = v;
+      else ws[(size_t)(b * S + sp) * (BS ? 2 : 1) * C + c] = v;
     }
+    if constexpr (BS) {
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < kMaxV; ++k) {
+        const int c = (lane + 64 * k) * 4;
+        if (c >= cb && c < cb + 512 && c < C) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) red[wave][c - cb + e] = acs[k][e];
+        }
+      }
+      __syncthreads();
+      for (int cl = threadIdx.x; cl < 512 && cb + cl < C; cl += 256) {
+        const int c = cb + cl;
+        const float v = ((red[0][cl] + red[1][cl]) + red[2][cl]) + red[3][cl];
+        if (S == 1) dsum[(size_t)b * ld_mod + c] = v;
+        else ws[((size_t)(b * S + sp) * 2 + 1) * C + c] = v;
+      }
+    }
+  }
+}
+
+// dbias[c] = sum over images b (in order) of gate[b][c] * dsum[b][c]
+__global__ void gate_bias_kernel(const float* gate, const float* dsum, int ld, int B, int C, float* dbias) {
+  for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < C; c += gridDim.x * blockDim.x) {
+    float s = 0.f;
+    for (int b = 0; b < B; ++b) s += gate[(size_t)b * ld + c] * dsum[(size_t)b * ld + c];
+    dbias[c] = s;
   }
 }
 
@@ -315,7 +366,8 @@ __global__ void gelu_fwd_kernel(const void* u, long rows, int C, int ld, Drop dr
   }
 }
 
-template <typename T>
+// TA: the storage type of da (T, or float for dmc_gelu_bwd_f32in: the GEMM that made da stored it unrounded)
+template <typename T, typename TA = T>
 __global__ void gelu_bwd_kernel(const void* da, const void* u, long rows, int C, int ld, Drop drop, void* du) {
   const uint32_t seed = drop.thresh ? drop.s() : 0u;
   const long total = rows * (C / 4);
@@ -323,7 +375,7 @@ __global__ void gelu_bwd_kernel(const void* da, const void* u, long rows, int C,
     const long r = q / (C / 4);
     const int c = (int)(q - r * (C / 4)) * 4;
     float g[4], v[4];
-    ld4<T>(da, (size_t)r * ld + c, g);
+    ld4<TA>(da, (size_t)r * ld + c, g);
     ld4<T>(u, (size_t)r * ld + c, v);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -442,12 +494,33 @@ extern "C" int dmc_ln_mod_fwd(int dtype, const float* x, const void* br, int ld_
   hipStream_t s = dmc::as_stream(stream);
   const int grid = (T + 3) / 4;
   if (dtype == DMC_F32)
-    ln_mod_fwd_kernel<float><<<grid, 256, 0, s>>>(x, br, ld_br, gate, shift, scale, ld_mod, T, C, L, eps, d, x_out, h,
-                                                  ld_h, mean, rstd);
+    ln_mod_fwd_kernel<float, false><<<grid, 256, 0, s>>>(x, br, ld_br, gate, shift, scale, ld_mod, T, C, L, eps, d,
+                                                         x_out, h, ld_h, mean, rstd, nullptr, nullptr);
   else
-    ln_mod_fwd_kernel<bf16_t><<<grid, 256, 0, s>>>(x, br, ld_br, gate, shift, scale, ld_mod, T, C, L, eps, d, x_out,
-                                                   h, ld_h, mean, rstd);
+    ln_mod_fwd_kernel<bf16_t, false><<<grid, 256, 0, s>>>(x, br, ld_br, gate, shift, scale, ld_mod, T, C, L, eps, d,
+                                                          x_out, h, ld_h, mean, rstd, nullptr, nullptr);
   return dmc::check_launch("dmc_ln_mod_fwd");
+}
+
+extern "C" int dmc_ln_affine_mod_fwd(int dtype, const float* x, const void* br, int ld_br, const float* gate,
+                                     const float* shift, const float* scale, int ld_mod, int T, int C, int L, float eps,
+                                     const float* gamma, const float* beta, uint32_t drop_seed,
+                                     const uint32_t* drop_seed_base, uint32_t drop_thresh, float drop_scale,
+                                     float* x_out, void* h, int ld_h, float* mean, float* rstd, void* stream) {
+  DMC_REQUIRE(C % 4 == 0 && C <= 64 * 4 * kMaxV && T % L == 0 && L > 0, "ln_affine_mod_fwd: C %d T %d L %d", C, T, L);
+  DMC_REQUIRE(ld_h % 4 == 0 && (!br || ld_br % 4 == 0) && ld_mod % 4 == 0, "ln_affine_mod_fwd: leading dims");
+  DMC_REQUIRE(!br || gate, "ln_affine_mod_fwd: a branch needs its gate");
+  DMC_REQUIRE(gamma && beta, "ln_affine_mod_fwd: gamma / beta");
+  const Drop d = make_drop(drop_seed, drop_seed_base, drop_thresh, drop_scale);
+  hipStream_t s = dmc::as_stream(stream);
+  const int grid = (T + 3) / 4;
+  if (dtype == DMC_F32)
+    ln_mod_fwd_kernel<float, true><<<grid, 256, 0, s>>>(x, br, ld_br, gate, shift, scale, ld_mod, T, C, L, eps, d,
+                                                        x_out, h, ld_h, mean, rstd, gamma, beta);
+  else
+    ln_mod_fwd_kernel<bf16_t, true><<<grid, 256, 0, s>>>(x, br, ld_br, gate, shift, scale, ld_mod, T, C, L, eps, d,
+                                                         x_out, h, ld_h, mean, rstd, gamma, beta);
+  return dmc::check_launch("dmc_ln_affine_mod_fwd");
 }
 
 namespace {
@@ -475,11 +548,58 @@ extern "C" int dmc_ln_mod_bwd(int dtype, const void* dh, int ld_dh, const float*
   float* ws = (float*)workspace;
   const dim3 g(B, S);
   if (dtype == DMC_F32)
-    ln_mod_bwd_kernel<float><<<g, 256, 0, s>>>(dh, ld_dh, x, mean, rstd, scale, ld_mod, C, L, dx, dscale, dshift, ws);
+    ln_mod_bwd_kernel<float, false><<<g, 256, 0, s>>>(dh, ld_dh, x, mean, rstd, scale, ld_mod, C, L, dx, dscale,
+                                                      dshift, ws, nullptr);
   else
-    ln_mod_bwd_kernel<bf16_t><<<g, 256, 0, s>>>(dh, ld_dh, x, mean, rstd, scale, ld_mod, C, L, dx, dscale, dshift, ws);
+    ln_mod_bwd_kernel<bf16_t, false><<<g, 256, 0, s>>>(dh, ld_dh, x, mean, rstd, scale, ld_mod, C, L, dx, dscale,
+                                                       dshift, ws, nullptr);
   if (S > 1) split_sum_kernel<<<grid_for((long)B * C), 256, 0, s>>>(ws, B, S, C, 2, dscale, dshift, ld_mod);
   return dmc::check_launch("dmc_ln_mod_bwd");
+}
+
+namespace {
+// The per-image channel sums A = sum dh * xhat (in dscale) and Hs = sum dh (in dshift) of the affine LayerNorm ->
+// dscale = gamma A + beta Hs (in place), dshift = Hs, dgamma = sum_b (1 + scale_b) A_b, dbeta = sum_b (1 + scale_b) Hs_b
+// (images in order: deterministic)
+__global__ void ln_affine_finish_kernel(float* dscale, const float* dshift, const float* scale, int ld_mod, int B, int C,
+                                        const float* gamma, const float* beta, float* dgamma, float* dbeta) {
+  for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < C; c += gridDim.x * blockDim.x) {
+    const float gm = gamma[c], bt = beta[c];
+    float dg = 0.f, db = 0.f;
+    for (int b = 0; b < B; ++b) {
+      const size_t i = (size_t)b * ld_mod + c;
+      const float A = dscale[i], Hs = dshift[i], s1 = 1.0f + scale[i];
+      dg += s1 * A;
+      db += s1 * Hs;
+      dscale[i] = gm * A + bt * Hs;
+    }
+    dgamma[c] = dg;
+    dbeta[c] = db;
+  }
+}
+}  // namespace
+
+extern "C" int dmc_ln_affine_mod_bwd(int dtype, const void* dh, int ld_dh, const float* x, const float* mean,
+                                     const float* rstd, const float* scale, int ld_mod, int T, int C, int L,
+                                     const float* gamma, const float* beta, float* dx, float* dscale, float* dshift,
+                                     float* dgamma, float* dbeta, void* workspace, void* stream) {
+  DMC_REQUIRE(C % 4 == 0 && C <= 64 * 4 * kMaxV && T % L == 0 && L > 0, "ln_affine_mod_bwd: C %d (<= %d) T %d L %d", C,
+              64 * 4 * kMaxV, T, L);
+  DMC_REQUIRE(gamma && beta && dgamma && dbeta, "ln_affine_mod_bwd: gamma / beta and their gradients");
+  hipStream_t s = dmc::as_stream(stream);
+  const int B = T / L;
+  const int S = workspace ? row_splits(B, L) : 1;
+  float* ws = (float*)workspace;
+  const dim3 g(B, S);
+  if (dtype == DMC_F32)
+    ln_mod_bwd_kernel<float, true><<<g, 256, 0, s>>>(dh, ld_dh, x, mean, rstd, scale, ld_mod, C, L, dx, dscale, dshift,
+                                                     ws, gamma);
+  else
+    ln_mod_bwd_kernel<bf16_t, true><<<g, 256, 0, s>>>(dh, ld_dh, x, mean, rstd, scale, ld_mod, C, L, dx, dscale,
+                                                      dshift, ws, gamma);
+  if (S > 1) split_sum_kernel<<<grid_for((long)B * C), 256, 0, s>>>(ws, B, S, C, 2, dscale, dshift, ld_mod);
+  ln_affine_finish_kernel<<<grid_for(C), 256, 0, s>>>(dscale, dshift, scale, ld_mod, B, C, gamma, beta, dgamma, dbeta);
+  return dmc::check_launch("dmc_ln_affine_mod_bwd");
 }
 
 extern "C" int dmc_gate_bwd(int dtype, const float* dy, const void* br, int ld_br, const float* gate, int ld_mod, int T,
@@ -494,11 +614,35 @@ extern "C" int dmc_gate_bwd(int dtype, const float* dy, const void* br, int ld_b
   float* ws = (float*)workspace;
   const dim3 g(B, S);
   if (dtype == DMC_F32)
-    gate_bwd_kernel<float><<<g, 256, 0, s>>>(dy, br, ld_br, gate, ld_mod, C, L, d, dbr, ld_dbr, dgate, ws);
+    gate_bwd_kernel<float, false><<<g, 256, 0, s>>>(dy, br, ld_br, gate, ld_mod, C, L, d, dbr, ld_dbr, dgate, ws,
+                                                    nullptr);
   else
-    gate_bwd_kernel<bf16_t><<<g, 256, 0, s>>>(dy, br, ld_br, gate, ld_mod, C, L, d, dbr, ld_dbr, dgate, ws);
+    gate_bwd_kernel<bf16_t, false><<<g, 256, 0, s>>>(dy, br, ld_br, gate, ld_mod, C, L, d, dbr, ld_dbr, dgate, ws,
+                                                     nullptr);
   if (S > 1) split_sum_kernel<<<grid_for((long)B * C), 256, 0, s>>>(ws, B, S, C, 1, dgate, nullptr, ld_mod);
   return dmc::check_launch("dmc_gate_bwd");
+}
+
+extern "C" int dmc_gate_bwd_bias(int dtype, const float* dy, const void* br, int ld_br, const float* gate, int ld_mod,
+                                 int T, int C, int L, uint32_t drop_seed, const uint32_t* drop_seed_base,
+                                 uint32_t drop_thresh, float drop_scale, void* dbr, int ld_dbr, float* dgate,
+                                 float* dsum, float* dbias, void* workspace, void* stream) {
+  DMC_REQUIRE(C % 4 == 0 && C <= 64 * 4 * kMaxV && T % L == 0 && L > 0, "gate_bwd_bias: C %d (<= %d) T %d L %d", C,
+              64 * 4 * kMaxV, T, L);
+  DMC_REQUIRE(dsum && dbias, "gate_bwd_bias: dsum / dbias");
+  const Drop d = make_drop(drop_seed, drop_seed_base, drop_thresh, drop_scale);
+  hipStream_t s = dmc::as_stream(stream);
+  const int B = T / L;
+  const int S = workspace ? row_splits(B, L) : 1;
+  float* ws = (float*)workspace;
+  const dim3 g(B, S);
+  if (dtype == DMC_F32)
+    gate_bwd_kernel<float, true><<<g, 256, 0, s>>>(dy, br, ld_br, gate, ld_mod, C, L, d, dbr, ld_dbr, dgate, ws, dsum);
+  else
+    gate_bwd_kernel<bf16_t, true><<<g, 256, 0, s>>>(dy, br, ld_br, gate, ld_mod, C, L, d, dbr, ld_dbr, dgate, ws, dsum);
+  if (S > 1) split_sum_kernel<<<grid_for((long)B * C), 256, 0, s>>>(ws, B, S, C, 2, dgate, dsum, ld_mod);
+  gate_bias_kernel<<<grid_for(C), 256, 0, s>>>(gate, dsum, ld_mod, B, C, dbias);
+  return dmc::check_launch("dmc_gate_bwd_bias");
 }
 
 extern "C" int dmc_gelu_fwd(int dtype, const void* u, long rows, int C, int ld, uint32_t drop_seed,
@@ -521,6 +665,17 @@ extern "C" int dmc_gelu_bwd(int dtype, const void* da, const void* u, long rows,
   if (dtype == DMC_F32) gelu_bwd_kernel<float><<<grid_for(rows * C / 4), 256, 0, s>>>(da, u, rows, C, ld, d, du);
   else gelu_bwd_kernel<bf16_t><<<grid_for(rows * C / 4), 256, 0, s>>>(da, u, rows, C, ld, d, du);
   return dmc::check_launch("dmc_gelu_bwd");
+}
+
+extern "C" int dmc_gelu_bwd_f32in(int dtype, const float* da, const void* u, long rows, int C, int ld, uint32_t drop_seed,
+                                  const uint32_t* drop_seed_base, uint32_t drop_thresh, float drop_scale, void* du,
+                                  void* stream) {
+  DMC_REQUIRE(C % 4 == 0 && ld % 4 == 0, "gelu_bwd_f32in: C %d ld %d", C, ld);
+  const Drop d = make_drop(drop_seed, drop_seed_base, drop_thresh, drop_scale);
+  hipStream_t s = dmc::as_stream(stream);
+  if (dtype == DMC_F32) gelu_bwd_kernel<float><<<grid_for(rows * C / 4), 256, 0, s>>>(da, u, rows, C, ld, d, du);
+  else gelu_bwd_kernel<bf16_t, float><<<grid_for(rows * C / 4), 256, 0, s>>>(da, u, rows, C, ld, d, du);
+  return dmc::check_launch("dmc_gelu_bwd_f32in");
 }
 
 extern "C" int dmc_timestep_embedding(const int64_t* t, int B, int dim, float max_period, float* out, void* stream) {

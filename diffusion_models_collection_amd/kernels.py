@@ -794,3 +794,88 @@ def batch_sum(x, rows, n, out):
 
 def patch_dgrad(dtok, ld, w, B, ht, wt, p, C, H, dx):
     check(LIB.dmc_patch_dgrad(ptr(dtok), ld, ptr(w), B, ht, wt, p, C, H, ptr(dx), L.stream()), "dmc_patch_dgrad")
+
+
+# ---- DiM: affine LayerNorm + modulation (csrc/dmc_dit.hip), the Mamba mixer (csrc/dmc_mamba.hip) ----------------
+def ln_affine_mod_fwd(dtype, x, T, C, L_, mod, ld_mod, off_shift, off_scale, eps, gamma, beta, h, ld_h, mean, rstd,
+                      br=None, ld_br=0, off_gate=0, drop=None, x_out=None):
+    seed, seed_base, thresh, scale = drop_args(drop)
+    check(LIB.dmc_ln_affine_mod_fwd(L.dtype_code(dtype), ptr(x), ptr(br), ld_br, _mod_ptr(mod, off_gate)
+                                    if br is not None else None, _mod_ptr(mod, off_shift), _mod_ptr(mod, off_scale),
+                                    ld_mod, T, C, L_, float(eps), ptr(gamma), ptr(beta), seed, seed_base, thresh, scale,
+                                    ptr(x_out), ptr(h), ld_h, ptr(mean), ptr(rstd), L.stream()),
+          "dmc_ln_affine_mod_fwd")
+
+
+def ln_affine_mod_bwd(dtype, dh, ld_dh, x, mean, rstd, mod, ld_mod, off_scale, T, C, L_, gamma, beta, dx, dmod,
+                      off_dscale, off_dshift, dgamma, dbeta):
+    ws = _rowsum_ws(T, C, L_, dx.device)
+    check(LIB.dmc_ln_affine_mod_bwd(L.dtype_code(dtype), ptr(dh), ld_dh, ptr(x), ptr(mean), ptr(rstd),
+                                    _mod_ptr(mod, off_scale), ld_mod, T, C, L_, ptr(gamma), ptr(beta), ptr(dx),
+                                    _mod_ptr(dmod, off_dscale), _mod_ptr(dmod, off_dshift), ptr(dgamma), ptr(dbeta),
+                                    ptr(ws), L.stream()), "dmc_ln_affine_mod_bwd")
+
+
+def gate_bwd_bias(dtype, dy, br, ld_br, mod, ld_mod, off_gate, T, C, L_, dbr, ld_dbr, dmod, off_dgate, dbias,
+                  drop=None):
+    """gate_bwd, plus the fp32 gradient dbias [C] of the bias of the branch's last Linear."""
+    seed, seed_base, thresh, scale = drop_args(drop)
+    ws = _rowsum_ws(T, C, L_, dy.device)
+    dsum = torch.empty(T // L_, ld_mod, dtype=torch.float32, device=dy.device)
+    check(LIB.dmc_gate_bwd_bias(L.dtype_code(dtype), ptr(dy), ptr(br), ld_br, _mod_ptr(mod, off_gate), ld_mod, T, C,
+                                L_, seed, seed_base, thresh, scale, ptr(dbr), ld_dbr, _mod_ptr(dmod, off_dgate),
+                                ptr(dsum), ptr(dbias), ptr(ws), L.stream()), "dmc_gate_bwd_bias")
+
+
+def gelu_bwd_f32in(dtype, da, u, rows, C, ld, du, drop=None):
+    """gelu_bwd with da as fp32 rows."""
+    seed, seed_base, thresh, scale = drop_args(drop)
+    check(LIB.dmc_gelu_bwd_f32in(L.dtype_code(dtype), ptr(da), ptr(u), rows, C, ld, seed, seed_base, thresh, scale,
+                                 ptr(du), L.stream()), "dmc_gelu_bwd_f32in")
+
+
+def _col_ptr(t, col):
+    """Device address of column `col` of the rows t [.., ld]."""
+    return t.data_ptr() + col * t.element_size()
+
+
+def causal_conv_silu_fwd(dtype, x, ld_x, w, bias, B, L_, E, u, ld_u, x_col=0):
+    check(LIB.dmc_causal_conv_silu_fwd(L.dtype_code(dtype), _col_ptr(x, x_col), ld_x, ptr(w), ptr(bias), B, L_, E,
+                                       ptr(u), ld_u, L.stream()), "dmc_causal_conv_silu_fwd")
+
+
+def causal_conv_silu_bwd(dtype, du, ld_du, x, ld_x, w, bias, B, L_, E, dx, ld_dx, dw, dbias, x_col=0, dx_col=0):
+    ws = SCRATCH.get(LIB.dmc_causal_conv_workspace(B, L_, E), du.device)
+    check(LIB.dmc_causal_conv_silu_bwd(L.dtype_code(dtype), ptr(du), ld_du, _col_ptr(x, x_col), ld_x, ptr(w), ptr(bias),
+                                       B, L_, E, _col_ptr(dx, dx_col), ld_dx, ptr(dw), ptr(dbias), ptr(ws), L.stream()),
+          "dmc_causal_conv_silu_bwd")
+
+
+def scan_chunk():
+    return LIB.dmc_scan_chunk()
+
+
+def scan_states(B, L_, E, N, device):
+    """The chunk-entry state buffer selective_scan_fwd fills and selective_scan_bwd reads (None for one chunk)."""
+    K_ = (L_ + scan_chunk() - 1) // scan_chunk()
+    return torch.empty(B, K_, E, N, dtype=torch.float32, device=device) if K_ > 1 else None
+
+
+def selective_scan_fwd(dtype, u, ld_u, z, ld_z, z_col, dpre, ld_dp, bc, ld_bc, b_col, c_col, A_log, D, dt_bias, B, L_,
+                       E, N, states, y, ld_y):
+    ws = SCRATCH.get(LIB.dmc_selective_scan_workspace(B, L_, E, N, 0), u.device) if states is not None else None
+    check(LIB.dmc_selective_scan_fwd(L.dtype_code(dtype), ptr(u), ld_u, _col_ptr(z, z_col), ld_z, ptr(dpre), ld_dp,
+                                     _col_ptr(bc, b_col), _col_ptr(bc, c_col), ld_bc, ptr(A_log), ptr(D), ptr(dt_bias),
+                                     B, L_, E, N, ptr(states), ptr(ws), ptr(y), ld_y, L.stream()),
+          "dmc_selective_scan_fwd")
+
+
+def selective_scan_bwd(dtype, dy, ld_dy, u, ld_u, z, ld_z, z_col, dpre, ld_dp, bc, ld_bc, b_col, c_col, A_log, D,
+                       dt_bias, B, L_, E, N, states, du, ld_du, dz, ld_dz, dz_col, ddpre, ld_ddp, dbc, ld_dbc, bc_col,
+                       dA_log, dD):
+    ws = SCRATCH.get(LIB.dmc_selective_scan_workspace(B, L_, E, N, 1), u.device)
+    check(LIB.dmc_selective_scan_bwd(L.dtype_code(dtype), ptr(dy), ld_dy, ptr(u), ld_u, _col_ptr(z, z_col), ld_z,
+                                     ptr(dpre), ld_dp, _col_ptr(bc, b_col), _col_ptr(bc, c_col), ld_bc, ptr(A_log),
+                                     ptr(D), ptr(dt_bias), B, L_, E, N, ptr(states), ptr(ws), ptr(du), ld_du,
+                                     _col_ptr(dz, dz_col), ld_dz, ptr(ddpre), ld_ddp, ptr(dbc), ld_dbc, bc_col,
+                                     ptr(dA_log), ptr(dD), L.stream()), "dmc_selective_scan_bwd")

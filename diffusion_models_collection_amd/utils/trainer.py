@@ -33,8 +33,8 @@ from .helpers import resolve_image_size
 
 
 def _is_dmc_model(m):
-    """A backbone run by one of this package's executors (UNet, DiT): flat gradients, fused optimizer, graphs."""
-    return type(m).__name__ in ("UNet", "DiT") and hasattr(m, "executor") and type(m).__module__.startswith(
+    """A backbone run by one of this package's executors (UNet, DiT, DiM): flat gradients, fused optimizer, graphs."""
+    return type(m).__name__ in ("UNet", "DiT", "DiM") and hasattr(m, "executor") and type(m).__module__.startswith(
         "diffusion_models_collection_amd")
 
 

@@ -426,6 +426,70 @@ int dmc_batch_sum(const float* x, long rows, long n, float* out, void* stream);
 int dmc_patch_dgrad(const float* dtok, int ld, const float* w, int B, int ht, int wt, int p, int C, int H, float* dx,
                     void* stream);
 
+/* ---- DiM backbone (models/dim.py of the reference; dmc_dit.hip, dmc_mamba.hip) ---------------------------------
+ * ln_affine_mod_fwd / bwd: MambaBlock / FeedForward / FinalLayer.forward (dim.py:131-134, :166-169, :201-203) with
+ *   nn.LayerNorm(hidden, eps=1e-6) (:101, :150, :193, elementwise affine): dmc_ln_mod_fwd / bwd with
+ *   h = (xhat * gamma + beta) * (1 + scale) + shift; the backward also writes dgamma / dbeta [C], the sums over all
+ *   T rows (per image in row order, then images in order). With gamma = 1, beta = 0 both equal the plain kernels
+ *   bitwise. */
+/* gate_bwd_bias: dmc_gate_bwd, plus dbias [C] = sum over all T rows of dy * gate * mask taken in fp32: the gradient
+ * of the bias of the branch's last Linear (FeedForward.mlp[3], dim.py:156; the attention fallback's out_proj, :112),
+ * which the weight-gradient kernel would otherwise sum from the rounded dbr rows. dsum: [B][ld_mod] scratch rows
+ * (the per-image sums of dy * mask). The workspace of dmc_dit_rowsum_workspace serves (two sums per split). */
+int dmc_gate_bwd_bias(int dtype, const float* dy, const void* br, int ld_br, const float* gate, int ld_mod, int T, int C,
+                      int L, uint32_t drop_seed, const uint32_t* drop_seed_base, uint32_t drop_thresh,
+                      float drop_scale, void* dbr, int ld_dbr, float* dgate, float* dsum, float* dbias, void* workspace,
+                      void* stream);
+/* gelu_bwd_f32in: dmc_gelu_bwd with da given as fp32 rows (pitch ld) whatever `dtype` is: the input-gradient GEMM of
+ * FeedForward.mlp[3] (dim.py:156) stores them unrounded, so du (and the mlp[0] bias gradient summed from it) carries
+ * one rounding, not two. u and du are in `dtype`. */
+int dmc_gelu_bwd_f32in(int dtype, const float* da, const void* u, long rows, int C, int ld, uint32_t drop_seed,
+                       const uint32_t* drop_seed_base, uint32_t drop_thresh, float drop_scale, void* du, void* stream);
+int dmc_ln_affine_mod_fwd(int dtype, const float* x, const void* br, int ld_br, const float* gate, const float* shift,
+                          const float* scale, int ld_mod, int T, int C, int L, float eps, const float* gamma,
+                          const float* beta, uint32_t drop_seed, const uint32_t* drop_seed_base, uint32_t drop_thresh,
+                          float drop_scale, float* x_out, void* h, int ld_h, float* mean, float* rstd, void* stream);
+int dmc_ln_affine_mod_bwd(int dtype, const void* dh, int ld_dh, const float* x, const float* mean, const float* rstd,
+                          const float* scale, int ld_mod, int T, int C, int L, const float* gamma, const float* beta,
+                          float* dx, float* dscale, float* dshift, float* dgamma, float* dbeta, void* workspace,
+                          void* stream);
+/* The token mixer mamba_ssm.Mamba(d_model, d_state=16, d_conv=4, expand=2) of MambaBlock (dim.py:104-109, :137),
+ * E = 2 * d_model inner channels, token rows [T = B*L][E] in `dtype` with the given pitches, parameters fp32.
+ * causal_conv_silu_fwd: Mamba's conv1d (Conv1d(E, E, 4, groups=E, padding=3), cut to L) + SiLU over the tokens of
+ *   each image: u[b,l,c] = SiLU(bias[c] + sum_k w[c][k] * x[b,l-3+k,c]), x[b,<0] = 0; w is [E][4].
+ * causal_conv_silu_bwd: dx rows, dw [E][4] and dbias [E] (sums over images and tokens in a fixed order) from du;
+ *   workspace: dmc_causal_conv_workspace bytes.
+ * selective_scan_fwd: Mamba's selective_scan_fn with delta_softplus, D and the z gate:
+ *   delta = softplus(dpre + dt_bias) (torch threshold 20), A = -exp(A_log) [E][N],
+ *   s_t = exp(delta_t * A) * s_{t-1} + delta_t * Bm_t * u_t (s_{-1} = 0 per image, fp32 state),
+ *   y_t = (sum_n Cm_t[n] * s_t[n] + D * u_t) * SiLU(z_t). Bm / Cm are [T][N] at pitch ld_bc. N must be 16.
+ *   dpre, Bm and Cm are fp32 rows whatever `dtype` is (u, z, y and the gradient rows are in `dtype`).
+ *   The token axis is cut into chunks of dmc_scan_chunk() tokens; states [B][chunks][E][N] receives the state at
+ *   the start of every chunk (all the backward keeps of the states); with more than one chunk states and workspace
+ *   (dmc_selective_scan_workspace(.., 0) bytes) are required.
+ * selective_scan_bwd: from dy: du, dz, ddpre (the gradient of the delta pre-activation) rows; dBm / dCm (sums over
+ *   the channels) as columns bc_col .. bc_col + 2N of the rows dbc (pitch ld_dbc; the columns behind them up to the
+ *   pitch are zeroed); dA_log [E][N] and dD [E] (sums over images and tokens). No atomics: every sum has a fixed
+ *   order. workspace: dmc_selective_scan_workspace(.., 1) bytes. The dt_proj bias gradient is the column sum of
+ *   ddpre (the weight-gradient kernel's wg_bias). */
+int dmc_causal_conv_silu_fwd(int dtype, const void* x, int ld_x, const float* w, const float* bias, int B, int L, int E,
+                             void* u, int ld_u, void* stream);
+size_t dmc_causal_conv_workspace(int B, int L, int E);
+int dmc_causal_conv_silu_bwd(int dtype, const void* du, int ld_du, const void* x, int ld_x, const float* w,
+                             const float* bias, int B, int L, int E, void* dx, int ld_dx, float* dw, float* dbias,
+                             void* workspace, void* stream);
+int dmc_scan_chunk(void);
+size_t dmc_selective_scan_workspace(int B, int L, int E, int N, int backward);
+int dmc_selective_scan_fwd(int dtype, const void* u, int ld_u, const void* z, int ld_z, const float* dpre, int ld_dp,
+                           const float* Bm, const float* Cm, int ld_bc, const float* A_log, const float* D,
+                           const float* dt_bias, int B, int L, int E, int N, float* states, void* workspace, void* y,
+                           int ld_y, void* stream);
+int dmc_selective_scan_bwd(int dtype, const void* dy, int ld_dy, const void* u, int ld_u, const void* z, int ld_z,
+                           const float* dpre, int ld_dp, const float* Bm, const float* Cm, int ld_bc, const float* A_log,
+                           const float* D, const float* dt_bias, int B, int L, int E, int N, const float* states,
+                           void* workspace, void* du, int ld_du, void* dz, int ld_dz, void* ddpre, int ld_ddp,
+                           void* dbc, int ld_dbc, int bc_col, float* dA_log, float* dD, void* stream);
+
 /* ---- Device-resident data path (datasets/base_dataset.py:96-128, train.py:107-128) ----
  * One training batch from a uint8 image bank [n_images][H][W][C] resident in device memory: out[b] =
  * Normalize(ToTensor(RandomHorizontalFlip(bank[idx[b]]))) as NCHW fp32 [B][C][H][W], i.e.
