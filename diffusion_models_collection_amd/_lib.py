@@ -17,6 +17,8 @@ DMC_F32, DMC_BF16 = 0, 1
 MODE_NORMAL, MODE_UPSAMPLE, MODE_DILATE = 0, 1, 2
 PRO_NONE, PRO_AFFINE_SILU, PRO_SILU, PRO_AFFINE, PRO_GN_SILU = 0, 1, 2, 3, 4
 LOSS = {"l1": 0, "l2": 1, "huber": 2}
+PRED = {"eps": 0, "v": 1}    # include/dmc.h DMC_PRED_*
+OBJECTIVE_MAX_BLOCKS = 64    # include/dmc.h DMC_OBJECTIVE_MAX_BLOCKS
 PACK_FWD, PACK_DGRAD, PACK_UPDGRAD = 0, 1, 2
 
 _c_int, _c_p, _c_f, _c_u32, _c_long, _c_size = (ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_uint32,
@@ -143,6 +145,10 @@ def _load():
         "dmc_q_sample": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_p, _c_p]),
         "dmc_loss_fwd": (_c_int, [_c_int, _c_p, _c_p, _c_long, _c_p, _c_p, _c_p]),
         "dmc_loss_bwd": (_c_int, [_c_int, _c_p, _c_p, _c_long, _c_p, _c_p, _c_p]),
+        "dmc_objective": (_c_int, [_c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int,
+                                   _c_p, _c_p, _c_p, _c_p, _c_p]),
+        "dmc_pred_convert": (_c_int, [_c_int, _c_p, _c_p, _c_p, _c_p, _c_int, _c_p, _c_int, _c_int, _c_int, _c_p,
+                                      _c_p, _c_p]),
         "dmc_ddim_step": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_f, _c_int, _c_p, _c_p,
                                    _c_p]),
         "dmc_ddpm_step": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int,

@@ -11,6 +11,8 @@
 //   label embedding     models/unet.py:183, 256-258
 //   EMA                 utils/trainer.py:187-202
 //   clip_grad_norm_     utils/trainer.py:259
+// Not in the reference: the DPM-Solver++ step (arXiv:2211.01095) and the v-prediction / min-SNR objective with its
+// output conversion (arXiv:2202.00512, arXiv:2303.09556), written to the same one-rounding-per-op rule.
 #include <stdlib.h>
 #include <string.h>
 #include "dmc_common.h"
@@ -202,6 +204,156 @@ __global__ void loss_bwd_kernel(int type, const float* pred, const float* target
     else if (type == DMC_LOSS_L1) v = (d > 0.f) ? 1.f : (d < 0.f ? -1.f : 0.f);
     else v = fabsf(d) < 1.f ? d : (d > 0.f ? 1.f : -1.f);
     dpred[i] = v * g;
+  }
+}
+
+// ---------------- objective: prediction target, per-sample weight, loss and gradient in one pass ----------------
+// v-prediction target (Salimans & Ho 2022, arXiv:2202.00512, eq. 31 / appendix D): v = alpha*eps - sigma*x0; min-SNR
+// weights (Hang et al. 2023, arXiv:2303.09556) come from the host as a [T] table (diffusion/_objective.py). One
+// element: target, the loss term of loss_partial_kernel and, when a gradient is asked for, loss_bwd_kernel's value;
+// every op is a separate rounding.
+DMC_DEV float obj_elem(int pred_type, int type, float sa, float s1, float p, float x0, float e, bool grad, float scale,
+                       float& dp) {
+  float target = e;
+  if (pred_type == DMC_PRED_V) {
+    const float a_ = sa * e;
+    const float b_ = s1 * x0;
+    target = a_ - b_;
+  }
+  if (grad) {
+    const float d = p - target;
+    float v;
+    if (type == DMC_LOSS_L2) v = 2.f * d;
+    else if (type == DMC_LOSS_L1) v = (d > 0.f) ? 1.f : (d < 0.f ? -1.f : 0.f);
+    else v = fabsf(d) < 1.f ? d : (d > 0.f ? 1.f : -1.f);
+    dp = v * scale;
+  }
+  return loss_elem(type, target - p);
+}
+
+DMC_DEV long clamp_t(long t, int T) { return t < 0 ? 0 : (t > T - 1 ? T - 1 : t); }   // never index past a table
+
+// Grid as dpm_step_kernel: blockIdx.y strides over samples, blockIdx.x over the sample's elements, so t and the
+// table entries are block-uniform, read once per sample. Block (bx, n) leaves its sum at partial[n * gridDim.x + bx];
+// pred / x0 / noise are read once and dpred written once in that same pass. x0 is read for v-prediction only.
+template <bool VEC>
+__global__ __launch_bounds__(256) void objective_kernel(int pred_type, int type, const float* pred, const float* x0,
+                                                        const float* noise, const int64_t* t, const float* sa,
+                                                        const float* s1, const float* w, int T, int N, int per,
+                                                        const float* dloss, float* dpred, float* partial) {
+  __shared__ float red[4];
+  const bool grad = dpred != nullptr;
+  const bool isv = pred_type == DMC_PRED_V;
+  const float g = grad ? dloss[0] / (float)((long)N * per) : 0.f;
+  for (int n = blockIdx.y; n < N; n += gridDim.y) {
+    const long tt = clamp_t(t[n], T);
+    const float san = isv ? sa[tt] : 0.f, s1n = isv ? s1[tt] : 0.f;
+    float scale = g;
+    if (w) scale = g * w[tt];
+    const size_t base = (size_t)n * per;
+    float s = 0.f;
+    if (VEC) {
+      const int per4 = per / 4;
+      for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < per4; q += gridDim.x * blockDim.x) {
+        const size_t i = base + (size_t)q * 4;
+        const v4f pv = *(const v4f*)(pred + i);
+        const v4f ev = *(const v4f*)(noise + i);
+        v4f xv = {0.f, 0.f, 0.f, 0.f}, dv = xv;
+        if (isv) xv = *(const v4f*)(x0 + i);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          float dp = 0.f;
+          s += obj_elem(pred_type, type, san, s1n, pv[k], xv[k], ev[k], grad, scale, dp);
+          dv[k] = dp;
+        }
+        if (grad) *(v4f*)(dpred + i) = dv;
+      }
+    } else {
+      for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < per; q += gridDim.x * blockDim.x) {
+        const size_t i = base + q;
+        float dp = 0.f;
+        s += obj_elem(pred_type, type, san, s1n, pred[i], isv ? x0[i] : 0.f, noise[i], grad, scale, dp);
+        if (grad) dpred[i] = dp;
+      }
+    }
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[(size_t)n * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    __syncthreads();   // red is reused by the block's next sample
+  }
+}
+
+// loss = (1/N) sum_n w[t_n] * (1/per) * (sample n's partials in block order), samples added in index order by one
+// thread: a fixed order, no atomics.
+__global__ __launch_bounds__(256) void objective_final_kernel(const float* partial, int gx, const int64_t* t,
+                                                              const float* w, int T, int N, int per, float* loss) {
+  __shared__ float sm[256];
+  float total = 0.f;
+  for (int n0 = 0; n0 < N; n0 += 256) {
+    const int n = n0 + threadIdx.x;
+    float m = 0.f;
+    if (n < N) {
+      float s = 0.f;
+      for (int b = 0; b < gx; ++b) s += partial[(size_t)n * gx + b];
+      m = s / (float)per;
+      if (w) m = w[clamp_t(t[n], T)] * m;
+    }
+    sm[threadIdx.x] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const int cnt = N - n0 < 256 ? N - n0 : 256;
+      for (int k = 0; k < cnt; ++k) total += sm[k];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) loss[0] = total / (float)N;
+}
+
+// v-prediction model output -> (eps, x0) for the step kernels; row r*N + n of pred pairs with x[n], t[n] (reps = 2:
+// the batched cond / uncond forward of CFG). x0 is formed directly, with no division by alpha.
+template <bool VEC>
+__global__ __launch_bounds__(256) void pred_convert_kernel(const float* x, const int64_t* t, const float* sa,
+                                                           const float* s1, int T, const float* pred, int reps,
+                                                           int N, int per, float* eps_out, float* x0_out) {
+  for (int n = blockIdx.y; n < N; n += gridDim.y) {
+    const long tt = clamp_t(t[n], T);
+    const float san = sa[tt], s1n = s1[tt];
+    const size_t xbase = (size_t)n * per;
+    for (int r = 0; r < reps; ++r) {
+      const size_t base = ((size_t)r * N + n) * per;
+      if (VEC) {
+        const int per4 = per / 4;
+        for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < per4; q += gridDim.x * blockDim.x) {
+          const v4f xv = *(const v4f*)(x + xbase + (size_t)q * 4);
+          const v4f pv = *(const v4f*)(pred + base + (size_t)q * 4);
+          v4f ev, x0v;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const float u = s1n * xv[k];
+            const float qq = san * pv[k];
+            ev[k] = u + qq;
+            const float p = san * xv[k];
+            const float rr = s1n * pv[k];
+            x0v[k] = p - rr;
+          }
+          *(v4f*)(eps_out + base + (size_t)q * 4) = ev;
+          if (x0_out) *(v4f*)(x0_out + base + (size_t)q * 4) = x0v;
+        }
+      } else {
+        for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < per; q += gridDim.x * blockDim.x) {
+          const float xx = x[xbase + q], pp = pred[base + q];
+          const float u = s1n * xx;
+          const float qq = san * pp;
+          eps_out[base + q] = u + qq;
+          if (x0_out) {
+            const float p = san * xx;
+            const float rr = s1n * pp;
+            x0_out[base + q] = p - rr;
+          }
+        }
+      }
+    }
   }
 }
 
@@ -676,6 +828,55 @@ extern "C" int dmc_loss_bwd(int type, const float* pred, const float* target, lo
   DMC_REQUIRE(type >= 0 && type <= 2, "loss: type %d", type);
   loss_bwd_kernel<<<grid_for(n), 256, 0, dmc::as_stream(stream)>>>(type, pred, target, n, dloss, dpred);
   return dmc::check_launch("dmc_loss_bwd");
+}
+
+namespace {
+// (gx, gy) of the sample-per-blockIdx.y kernels: at most xcap blocks along a sample, at most 16384 blocks in all
+inline dim3 sample_grid(int units, int N, int xcap) {
+  const int gx = grid_for(units, 256, xcap);
+  const int gy_cap = 16384 / gx > 0 ? 16384 / gx : 1;
+  return dim3(gx, N < gy_cap ? N : gy_cap);
+}
+}  // namespace
+
+extern "C" int dmc_objective(int pred_type, int type, const float* pred, const float* x0, const float* noise,
+                             const int64_t* t, const float* sa, const float* s1, const float* w, int T, int N, int per,
+                             const float* dloss, float* loss, float* dpred, float* ws, void* stream) {
+  DMC_REQUIRE(pred_type == DMC_PRED_EPS || pred_type == DMC_PRED_V, "objective: prediction type %d", pred_type);
+  DMC_REQUIRE(type >= 0 && type <= 2, "objective: loss type %d", type);
+  DMC_REQUIRE(T > 0 && N > 0 && per > 0, "objective: T %d, N %d, per_sample %d must be positive", T, N, per);
+  DMC_REQUIRE(pred && noise && t && loss && ws, "objective: pred, noise, t, loss and workspace must not be NULL");
+  DMC_REQUIRE(pred_type == DMC_PRED_EPS || (x0 && sa && s1), "objective: v-prediction needs x0 and both tables");
+  DMC_REQUIRE(!dpred || dloss, "objective: dpred needs the upstream gradient dloss");
+  const uintptr_t bits = (uintptr_t)pred | (uintptr_t)noise | (uintptr_t)dpred |
+                         (pred_type == DMC_PRED_V ? (uintptr_t)x0 : 0);   // a NULL or unread operand adds no bits
+  const bool vec = per % 4 == 0 && (bits & 15) == 0;
+  const dim3 grid = sample_grid(vec ? per / 4 : per, N, DMC_OBJECTIVE_MAX_BLOCKS);
+  hipStream_t s = dmc::as_stream(stream);
+  if (vec)
+    objective_kernel<true><<<grid, 256, 0, s>>>(pred_type, type, pred, x0, noise, t, sa, s1, w, T, N, per, dloss, dpred,
+                                                ws);
+  else
+    objective_kernel<false><<<grid, 256, 0, s>>>(pred_type, type, pred, x0, noise, t, sa, s1, w, T, N, per, dloss,
+                                                 dpred, ws);
+  objective_final_kernel<<<1, 256, 0, s>>>(ws, (int)grid.x, t, w, T, N, per, loss);
+  return dmc::check_launch("dmc_objective");
+}
+
+extern "C" int dmc_pred_convert(int pred_type, const float* x, const int64_t* t, const float* sa, const float* s1,
+                                int T, const float* pred, int reps, int N, int per, float* eps_out, float* x0_out,
+                                void* stream) {
+  DMC_REQUIRE(pred_type == DMC_PRED_V, "pred_convert: prediction type %d (eps needs no conversion)", pred_type);
+  DMC_REQUIRE(T > 0 && N > 0 && per > 0 && reps > 0,
+              "pred_convert: T %d, N %d, per_sample %d, reps %d must be positive", T, N, per, reps);
+  DMC_REQUIRE(x && t && sa && s1 && pred && eps_out, "pred_convert: only x0_out may be NULL");
+  const uintptr_t bits = (uintptr_t)x | (uintptr_t)pred | (uintptr_t)eps_out | (uintptr_t)x0_out;
+  const bool vec = per % 4 == 0 && (bits & 15) == 0;
+  const dim3 grid = sample_grid(vec ? per / 4 : per, N, 8192);
+  hipStream_t s = dmc::as_stream(stream);
+  if (vec) pred_convert_kernel<true><<<grid, 256, 0, s>>>(x, t, sa, s1, T, pred, reps, N, per, eps_out, x0_out);
+  else pred_convert_kernel<false><<<grid, 256, 0, s>>>(x, t, sa, s1, T, pred, reps, N, per, eps_out, x0_out);
+  return dmc::check_launch("dmc_pred_convert");
 }
 
 extern "C" int dmc_ddim_step(const float* x, const float* eps, const float* x0_in, const int64_t* t, const int64_t* t_next,

@@ -10,6 +10,8 @@ clamp, sigma, direction term and the eta>0 noise. The reference's `t_next.min() 
 is done on device: if any t_next < 0, alpha_next = 1 for the whole batch, exactly as the reference.
 CFG batches the cond/uncond forwards into one 2B forward and fuses combine + x0 + dynamic threshold
 (per-row torch.quantile restatement) into dmc_cfg_x0.
+prediction_type='v' (not in the reference; ddpm.py ObjectiveMixin): one dmc_pred_convert launch after the model call
+hands eps and x0 to the same step kernel.
 """
 import os
 
@@ -17,16 +19,17 @@ import torch
 from tqdm import tqdm
 
 from .. import kernels as K
-from . import _schedule
+from . import _objective, _schedule
 from ._graph import StepGraph, cache_for, run_loop
-from .ddpm import DDPM, _require_cuda, diffusion_loss, make_betas
+from .ddpm import ObjectiveMixin, _require_cuda, diffusion_loss, make_betas
 
 
-class DDIM:
+class DDIM(ObjectiveMixin):
     """DDIM diffusion process with accelerated sampling (diffusion/ddim.py:13-351)."""
 
     def __init__(self, num_timesteps=1000, num_inference_steps=50, beta_start=0.0001, beta_end=0.02,
-                 beta_schedule='linear', eta=0.0, device='cuda'):
+                 beta_schedule='linear', eta=0.0, device='cuda', prediction_type='eps'):
+        self.prediction_type = _objective.check_prediction_type(prediction_type)
         self.num_timesteps = num_timesteps
         self.num_inference_steps = num_inference_steps
         self.eta = eta
@@ -58,12 +61,15 @@ class DDIM:
         return K.q_sample(x_start.float(), noise.float(), t.to(dev).long().contiguous(),
                           self._tab("sqrt_alphas_cumprod", dev), self._tab("sqrt_one_minus_alphas_cumprod", dev))
 
-    def p_losses(self, model, x_start, t, y=None, noise=None, loss_type='l2'):
+    def p_losses(self, model, x_start, t, y=None, noise=None, loss_type='l2', snr_gamma=None):
+        """As DDPM.p_losses (snr_gamma and the v target are not in the reference)."""
         if noise is None:
             noise = torch.randn_like(x_start)
         x_noisy = self.q_sample(x_start, t, noise)
         predicted_noise = model(x_noisy, t, y)
-        return diffusion_loss(predicted_noise, noise, loss_type)
+        if self._default_objective(snr_gamma):
+            return diffusion_loss(predicted_noise, noise, loss_type)
+        return self._objective_loss(predicted_noise, x_start, noise, t, loss_type, snr_gamma)
 
     def _extract(self, a, t, x_shape):
         batch_size = t.shape[0]
@@ -76,6 +82,8 @@ class DDIM:
         """x_t -> x_{t_next} (diffusion/ddim.py:154-208), one fused kernel after the model call."""
         if eps is None:
             eps = model(x, t, y)
+            if self.prediction_type == "v":
+                eps, x0_pred = self._convert(eps, x, t)
         _require_cuda(x, eps)
         dev = x.device
         z = None
@@ -129,8 +137,10 @@ class DDIM:
         def fn(x, t, tn, *rest):
             yy = rest[0] if has_y else None
             z = rest[-1] if len(rest) > has_y else None
-            eps = model(x, t[:1], None) if shared_t else None
-            return self.p_sample(model, x, t, tn, yy, eps=eps, noise=z)
+            eps, x0 = (model(x, t[:1], None) if shared_t else None), None
+            if eps is not None and self.prediction_type == "v":
+                eps, x0 = self._convert(eps, x, t)
+            return self.p_sample(model, x, t, tn, yy, eps=eps, x0_pred=x0, noise=z)
 
         def record(i, x):
             bar.update(1)
@@ -138,7 +148,8 @@ class DDIM:
                 imgs.append(x.cpu())
 
         cache = None if return_all_timesteps else cache_for(
-            model, ("ddim", self.eta, shared_t, has_y, has_z, self.alphas_cumprod.data_ptr()), self, img)
+            model, ("ddim", self.prediction_type, self.eta, shared_t, has_y, has_z, self.alphas_cumprod.data_ptr()),
+            self, img)
         img = run_loop(img, S, inputs, fn, StepGraph.eligible(model, img, True, False),
                        record, cache=cache, const=(3,) if has_y else ())
         bar.close()
@@ -172,7 +183,7 @@ class DDIM:
             return (x, tab[i], tab[i + 1], y) + ((z,) if z is not None else ())
 
         def fn(x, t, tn, yy, z=None):
-            eps_c, eps_u = DDPM._cfg_eps(model, x, t, yy)
+            eps_c, eps_u = self._cfg_pair(model, x, t, yy)
             eps_g, x0 = K.cfg_x0(x.contiguous(), eps_c.contiguous(), eps_u.contiguous(), cfg_scale, t, ac, None, 0,
                                  p_threshold)
             return self.p_sample(model, x, t, tn, y=None, clip_denoised=False, eps=eps_g, x0_pred=x0, noise=z)
@@ -183,7 +194,8 @@ class DDIM:
                 imgs.append(x.cpu())
 
         cache = None if return_all_timesteps else cache_for(
-            model, ("ddim_cfg", self.eta, has_z, float(cfg_scale), p_threshold, ac.data_ptr()), self, img)
+            model, ("ddim_cfg", self.prediction_type, self.eta, has_z, float(cfg_scale), p_threshold, ac.data_ptr()),
+            self, img)
         img = run_loop(img, S, inputs, fn, StepGraph.eligible(model, img, True, False),
                        record, cache=cache, const=(3,))
         bar.close()

@@ -7,6 +7,8 @@ Arithmetic runs in fused HIP kernels (libdmc.so):
   p_losses loss       -> dmc_loss_fwd / dmc_loss_bwd (deterministic reduction), via _LossFn
   p_sample / mean     -> dmc_ddpm_step (x0 prediction, clip, posterior mean, noise, one launch)
   CFG + threshold     -> dmc_cfg_x0 (combine, x0, per-row quantile, clamp, one launch)
+  v / min-SNR loss    -> dmc_objective (target, weight, loss and gradient in one pass), via _ObjectiveFn
+  v model output      -> dmc_pred_convert (eps and x0 for the step kernels, one launch after the model call)
 The cond/uncond forwards of CFG are batched into ONE 2B forward.
 
 Schedule tables are built on the host by _schedule.py: the reference's op sequence as explicit IEEE fp32
@@ -15,13 +17,16 @@ then uploaded once.
 
 Extra optional keyword arguments (not in the reference, all default to the reference behaviour):
 p_sample(noise=...), sample(x_T=...), sample_with_cfg(x_T=...) inject the Gaussian draws for parity tests.
+DDPM(prediction_type='v') trains and samples a v-prediction network (arXiv:2202.00512), p_losses(snr_gamma=...)
+weights each sample by min-SNR-gamma (arXiv:2303.09556); see _objective.py. With the defaults neither launches
+anything new.
 """
 import torch
 import torch.nn.functional as F
 from tqdm import tqdm
 
 from .. import kernels as K
-from . import _schedule
+from . import _objective, _schedule
 from ._graph import StepGraph, run_loop
 
 
@@ -62,10 +67,84 @@ def diffusion_loss(pred, target, loss_type):
     return _LossFn.apply(pred, target, loss_type)
 
 
-class DDPM:
+class _ObjectiveFn(torch.autograd.Function):
+    """The loss for a v target and / or per-sample weights (dmc_objective): the forward is the kernel without a
+    gradient output, the backward the same kernel with the upstream scalar."""
+
+    @staticmethod
+    def forward(ctx, pred, x0, noise, t, sa, s1, w, pred_type, loss_type):
+        pred = pred.contiguous().float()
+        ctx.save_for_backward(pred, x0, noise, t, sa, s1, w)
+        ctx.types = (pred_type, loss_type)
+        return K.objective(pred_type, loss_type, pred, x0, noise, t, sa, s1, w, grad=False)[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, x0, noise, t, sa, s1, w = ctx.saved_tensors
+        _, dpred = K.objective(*ctx.types, pred, x0, noise, t, sa, s1, w, dloss=g.contiguous().float())
+        return (dpred,) + (None,) * 8
+
+
+class ObjectiveMixin:
+    """prediction_type, the min-SNR weight tables and the two launches they need, shared by DDPM and DDIM (and so
+    DPMSolver): both carry sqrt_alphas_cumprod / sqrt_one_minus_alphas_cumprod and _tab()."""
+
+    prediction_type = "eps"
+
+    def set_prediction_type(self, prediction_type):
+        """'eps' or 'v'. Drops the sampler's cached step graphs (their steps were captured for the old type)."""
+        self.prediction_type = _objective.check_prediction_type(prediction_type)
+        self.__dict__.pop("_step_graphs", None)
+
+    def _snr_weights(self, gamma, dev):
+        """[T] fp32 device table of min-SNR-gamma weights for the current prediction type, built and uploaded once
+        per (gamma, prediction type)."""
+        key = (_objective.check_gamma(gamma), self.prediction_type)
+        cache = self.__dict__.setdefault("_snr_tables", {})
+        w = cache.get(key)
+        if w is None or w.device != dev:
+            w = torch.from_numpy(_objective.min_snr_weights(self.alphas_cumprod.cpu().numpy(), *key)).to(dev)
+            cache[key] = w
+        return w
+
+    def _default_objective(self, snr_gamma):
+        return self.prediction_type == "eps" and snr_gamma is None
+
+    def _objective_loss(self, pred, x_start, noise, t, loss_type, snr_gamma):
+        if loss_type not in ("l1", "l2", "huber"):
+            raise ValueError(f"Unknown loss type: {loss_type}")
+        _require_cuda(pred, x_start, noise)
+        dev = pred.device
+        w = None if snr_gamma is None else self._snr_weights(snr_gamma, dev)
+        return _ObjectiveFn.apply(pred, x_start.contiguous().float(), noise.contiguous().float(),
+                                  t.to(dev).long().contiguous(), self._tab("sqrt_alphas_cumprod", dev),
+                                  self._tab("sqrt_one_minus_alphas_cumprod", dev), w, self.prediction_type, loss_type)
+
+    def _convert(self, out, x, t, want_x0=True):
+        """(eps, x0 or None) from a v-prediction model output; out may hold 2B rows (CFG)."""
+        _require_cuda(x, out)
+        dev = x.device
+        return K.pred_convert("v", x.contiguous().float(), t.to(dev).long().contiguous(),
+                              self._tab("sqrt_alphas_cumprod", dev), self._tab("sqrt_one_minus_alphas_cumprod", dev),
+                              out.contiguous().float(), want_x0=want_x0)
+
+    def _cfg_pair(self, model, img, t, y):
+        """DDPM._cfg_eps for either prediction type: a v output is converted to eps (both halves, one launch)
+        before the guidance, which is affine with coefficients summing to 1 and so commutes with the conversion."""
+        B = img.shape[0]
+        if self.prediction_type == "eps":
+            return DDPM._cfg_eps(model, img, t, y)
+        both = model(torch.cat([img, img], 0), torch.cat([t, t], 0), torch.cat([y, torch.zeros_like(y)], 0))
+        eps, _ = self._convert(both, img, t, want_x0=False)
+        return eps[:B], eps[B:]
+
+
+class DDPM(ObjectiveMixin):
     """DDPM diffusion process (diffusion/ddpm.py:15-332)."""
 
-    def __init__(self, num_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule='linear', device='cuda'):
+    def __init__(self, num_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule='linear', device='cuda',
+                 prediction_type='eps'):
+        self.prediction_type = _objective.check_prediction_type(prediction_type)
         self.num_timesteps = num_timesteps
         self.device = device
         tabs = _schedule.build_tables(num_timesteps, beta_start, beta_end, beta_schedule)
@@ -91,13 +170,16 @@ class DDPM:
         return K.q_sample(x_start.float(), noise.float(), t.to(dev).long().contiguous(),
                           self._tab("sqrt_alphas_cumprod", dev), self._tab("sqrt_one_minus_alphas_cumprod", dev))
 
-    def p_losses(self, model, x_start, t, y=None, noise=None, loss_type='l2'):
-        """Training loss (diffusion/ddpm.py:106-140)."""
+    def p_losses(self, model, x_start, t, y=None, noise=None, loss_type='l2', snr_gamma=None):
+        """Training loss (diffusion/ddpm.py:106-140). Not in the reference: snr_gamma (min-SNR-gamma weighting) and
+        the v target of prediction_type='v', both through dmc_objective."""
         if noise is None:
             noise = torch.randn_like(x_start)
         x_noisy = self.q_sample(x_start, t, noise)
         predicted_noise = model(x_noisy, t, y)
-        return diffusion_loss(predicted_noise, noise, loss_type)
+        if self._default_objective(snr_gamma):
+            return diffusion_loss(predicted_noise, noise, loss_type)
+        return self._objective_loss(predicted_noise, x_start, noise, t, loss_type, snr_gamma)
 
     def _extract(self, a, t, x_shape):
         batch_size = t.shape[0]
@@ -118,6 +200,8 @@ class DDPM:
         """Posterior mean / variance / log-variance (diffusion/ddpm.py:151-195)."""
         if eps is None:
             eps = model(x, t, y)
+            if self.prediction_type == "v":
+                eps, x0_pred = self._convert(eps, x, t)
         _require_cuda(x, eps)
         mean = self._step(x, eps, t, clip_denoised, x0_pred, None)
         var = self._extract(self.posterior_variance, t, x.shape)
@@ -129,6 +213,8 @@ class DDPM:
         """x_{t-1} ~ p(x_{t-1} | x_t) (diffusion/ddpm.py:197-220), one fused kernel after the model call."""
         if eps is None:
             eps = model(x, t, y)
+            if self.prediction_type == "v":
+                eps, x0_pred = self._convert(eps, x, t)
         if noise is None:
             noise = torch.randn_like(x)
         _require_cuda(x, eps, noise)
@@ -199,7 +285,7 @@ class DDPM:
             return x, ts[T - 1 - i], self._noise(noise, i, x)
 
         def fn(x, t, z):
-            eps_c, eps_u = self._cfg_eps(model, x, t, y)
+            eps_c, eps_u = self._cfg_pair(model, x, t, y)
             eps_g, x0 = K.cfg_x0(x.contiguous(), eps_c.contiguous(), eps_u.contiguous(), cfg_scale, t,
                                  self._tab("sqrt_recip_alphas_cumprod", dev),
                                  self._tab("sqrt_recipm1_alphas_cumprod", dev), 1, p_threshold)

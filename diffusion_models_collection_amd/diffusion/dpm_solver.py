@@ -10,7 +10,8 @@ clamp, update, history write). The loop state is a [2, B, C, H, W] tensor, x and
 the step function's first input and its output, so the history rides through graph replays (diffusion/_graph.py)
 and a cached graph that replays from step 0 starts from the caller's fresh state. Row 0 has c1 = 0 and never reads
 the history, so the same captured step serves every i. CFG reuses dmc_cfg_x0 (guided eps, x0, dynamic threshold)
-unchanged and hands its x0 to dmc_dpm_step.
+unchanged and hands its x0 to dmc_dpm_step. With prediction_type='v' (ddpm.py ObjectiveMixin) dmc_pred_convert turns
+the model output into that x0 (plain path) or into the two eps halves (CFG) first.
 """
 import os
 
@@ -21,7 +22,7 @@ from .. import kernels as K
 from . import _dpm
 from ._graph import StepGraph, cache_for, run_loop
 from .ddim import DDIM
-from .ddpm import DDPM, _require_cuda
+from .ddpm import _require_cuda
 
 
 class DPMSolver(DDIM):
@@ -29,7 +30,7 @@ class DPMSolver(DDIM):
 
     def __init__(self, num_timesteps=1000, num_inference_steps=20, beta_start=0.0001, beta_end=0.02,
                  beta_schedule='linear', solver_order=2, timestep_spacing='logsnr', lower_order_final=True,
-                 device='cuda'):
+                 device='cuda', prediction_type='eps'):
         if solver_order not in (1, 2):
             raise ValueError(f"solver_order must be 1 or 2, got {solver_order}")
         if timestep_spacing not in _dpm.SPACINGS:
@@ -38,7 +39,7 @@ class DPMSolver(DDIM):
         self.timestep_spacing = timestep_spacing
         self.lower_order_final = bool(lower_order_final)
         super().__init__(num_timesteps, num_inference_steps, beta_start, beta_end, beta_schedule, eta=0.0,
-                         device=device)
+                         device=device, prediction_type=prediction_type)
 
     def _setup_inference_timesteps(self):
         """num_inference_steps keeps the request; with 'logsnr' len(inference_timesteps) can be below it."""
@@ -68,8 +69,8 @@ class DPMSolver(DDIM):
         return st
 
     def _key(self, tag, coef, *rest):
-        return (tag, self.solver_order, self.timestep_spacing, self.lower_order_final, coef.shape[0],
-                coef.data_ptr()) + rest
+        return (tag, self.prediction_type, self.solver_order, self.timestep_spacing, self.lower_order_final,
+                coef.shape[0], coef.data_ptr()) + rest
 
     def _run(self, model, st, S, inputs, fn, return_all_timesteps, key, const, desc):
         imgs = []
@@ -113,7 +114,11 @@ class DPMSolver(DDIM):
             x = st[0]
             eps = model(x, t[:1] if shared_t else t, yy)
             new = torch.empty_like(st)
-            K.dpm_step(x, eps.contiguous().float(), k, coef, clip=clip, x0_prev=st[1], out=new[0], x0_out=new[1])
+            if self.prediction_type == "v":
+                _, x0 = self._convert(eps, x, t)
+                K.dpm_step(x, None, k, coef, clip=clip, x0=x0, x0_prev=st[1], out=new[0], x0_out=new[1])
+            else:
+                K.dpm_step(x, eps.contiguous().float(), k, coef, clip=clip, x0_prev=st[1], out=new[0], x0_out=new[1])
             return new
 
         key = self._key("dpm", coef, clip, shared_t, has_y, self.alphas_cumprod.data_ptr())
@@ -144,7 +149,7 @@ class DPMSolver(DDIM):
 
         def fn(st, t, k, yy):
             x = st[0]
-            eps_c, eps_u = DDPM._cfg_eps(model, x, t, yy)
+            eps_c, eps_u = self._cfg_pair(model, x, t, yy)
             _, x0 = K.cfg_x0(x, eps_c.contiguous(), eps_u.contiguous(), cfg_scale, t, ac, None, 0, p_threshold)
             new = torch.empty_like(st)
             K.dpm_step(x, None, k, coef, clip=False, x0=x0, x0_prev=st[1], out=new[0], x0_out=new[1])

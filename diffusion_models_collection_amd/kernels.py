@@ -615,6 +615,90 @@ def loss_bwd(loss_type, pred, target, dloss):
     return dpred
 
 
+def _fp32_contig(what, *ts):
+    for t in ts:
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise L.DMCError(f"{what}: operands must be contiguous fp32, got {t.dtype} strides {t.stride()}")
+
+
+def _tables(what, dev, *tabs):
+    """Length of the [T] fp32 device tables (all the same length; None entries are skipped)."""
+    T = None
+    for tab in tabs:
+        if tab is None:
+            continue
+        if (tab.dim() != 1 or tab.numel() < 1 or tab.dtype != torch.float32 or tab.device != dev
+                or not tab.is_contiguous() or (T is not None and tab.numel() != T)):
+            raise L.DMCError(f"{what}: tables must be contiguous fp32 [T] tensors of one length on {dev}, got "
+                             f"{tab.dtype} {tuple(tab.shape)} on {tab.device}")
+        T = tab.numel()
+    return T
+
+
+def _pred_code(what, pred_type):
+    if pred_type not in L.PRED:
+        raise L.DMCError(f"{what}: unknown prediction type {pred_type!r}")
+    return L.PRED[pred_type]
+
+
+def objective(pred_type, loss_type, pred, x0, noise, t, sa, s1, w=None, dloss=None, grad=True, out=None):
+    """Loss and its gradient in one pass (dmc_objective): target = noise ('eps') or sa[t]*noise - s1[t]*x0 ('v'), a
+    per-sample weight w[t] (None: 1), mean over samples of the per-sample means. grad=False is the forward alone.
+    Returns (loss, dpred or None); dloss: the upstream gradient, a device scalar; out: the dpred buffer to fill."""
+    what = "dmc_objective"
+    code = _pred_code(what, pred_type)
+    if loss_type not in L.LOSS:
+        raise L.DMCError(f"{what}: unknown loss type {loss_type!r}")
+    if not pred.is_cuda or pred.dim() < 1 or pred.numel() < 1:
+        raise L.DMCError(f"{what}: pred must be a non-empty device tensor, got {tuple(pred.shape)} on {pred.device}")
+    N = pred.shape[0]
+    _same(pred, x0, noise, what=what)
+    _fp32_contig(what, pred, x0, noise)
+    _steps(N, pred.device, t, what=what)
+    T = _tables(what, pred.device, sa, s1, w)
+    if t is None or T is None or sa is None or s1 is None:
+        raise L.DMCError(f"{what}: needs timesteps and the sqrt_alphas_cumprod / sqrt_one_minus_alphas_cumprod tables")
+    dpred = None
+    if grad:
+        if dloss is None or dloss.numel() != 1 or dloss.dtype != torch.float32 or dloss.device != pred.device:
+            raise L.DMCError(f"{what}: dloss must be one fp32 value on {pred.device}")
+        dpred = torch.empty_like(pred) if out is None else out
+        _same(pred, dpred, what=what)
+        _fp32_contig(what, dpred)
+    loss = torch.empty((), dtype=torch.float32, device=pred.device)
+    ws = SCRATCH.get(L.OBJECTIVE_MAX_BLOCKS * N * 4, pred.device)
+    check(LIB.dmc_objective(code, L.LOSS[loss_type], ptr(pred), ptr(x0), ptr(noise), ptr(t), ptr(sa), ptr(s1), ptr(w),
+                            T, N, pred.numel() // N, ptr(dloss) if grad else None, ptr(loss), ptr(dpred), ptr(ws),
+                            L.stream()), what)
+    return loss, dpred
+
+
+def pred_convert(pred_type, x, t, sa, s1, pred, want_x0=True, out=None):
+    """(eps, x0 or None) from a v-prediction model output (dmc_pred_convert). pred holds reps * N rows for x's N:
+    row r*N + n pairs with x[n], t[n] (reps = 2: the batched cond / uncond forward of CFG). out: the buffers to fill."""
+    what = "dmc_pred_convert"
+    code = _pred_code(what, pred_type)
+    if code == L.PRED["eps"]:
+        raise L.DMCError(f"{what}: an eps prediction needs no conversion")
+    if not x.is_cuda or x.dim() < 1 or x.numel() < 1:
+        raise L.DMCError(f"{what}: x must be a non-empty device tensor, got {tuple(x.shape)} on {x.device}")
+    N = x.shape[0]
+    reps = pred.shape[0] // N if pred.dim() == x.dim() else 0
+    if reps < 1 or pred.shape != (reps * N,) + tuple(x.shape[1:]) or pred.device != x.device:
+        raise L.DMCError(f"{what}: pred {tuple(pred.shape)} on {pred.device} is not reps x {tuple(x.shape)} on "
+                         f"{x.device}")
+    eps, x0 = out if out is not None else (torch.empty_like(pred), torch.empty_like(pred) if want_x0 else None)
+    _same(pred, eps, x0, what=what)
+    _fp32_contig(what, x, pred, eps, x0)
+    _steps(N, x.device, t, what=what)
+    T = _tables(what, x.device, sa, s1)
+    if t is None or T is None or sa is None or s1 is None:
+        raise L.DMCError(f"{what}: needs timesteps and the sqrt_alphas_cumprod / sqrt_one_minus_alphas_cumprod tables")
+    check(LIB.dmc_pred_convert(code, ptr(x), ptr(t), ptr(sa), ptr(s1), T, ptr(pred), reps, N, x.numel() // N, ptr(eps),
+                               ptr(x0), L.stream()), what)
+    return eps, x0
+
+
 def ddim_step(x, eps, t, t_next, alphas_cumprod, eta=0.0, clip=True, x0=None, z=None, out=None):
     if out is None:
         out = torch.empty_like(x)

@@ -290,7 +290,8 @@ class GraphedTrainStep:
                 and _is_dmc_model(trainer._raw_model))
 
     def _key(self, images, y):
-        return (tuple(images.shape), images.device, None if y is None else tuple(y.shape))
+        return (tuple(images.shape), images.device, None if y is None else tuple(y.shape),
+                getattr(self.tr.diffusion, "prediction_type", "eps"))
 
     def _capture(self, images, y):
         tr = self.tr
@@ -306,6 +307,14 @@ class GraphedTrainStep:
         self.ring = [torch.zeros(16, dtype=torch.float32).pin_memory() for _ in range(self.RING)]
         self.ring_ev = [None] * self.RING
         self.slot = 0
+        # the objective when it is not the reference's: (prediction type, the two tables, the min-SNR weight table or
+        # None), looked up here so that a table's first upload never lands inside the capture
+        df = tr.diffusion
+        self.objective = None
+        if getattr(df, "prediction_type", "eps") != "eps" or tr.snr_gamma is not None:
+            w = None if tr.snr_gamma is None else df._snr_weights(tr.snr_gamma, dev)
+            self.objective = (df.prediction_type, df._tab("sqrt_alphas_cumprod", dev),
+                              df._tab("sqrt_one_minus_alphas_cumprod", dev), w)
         self.use_ema = f.uses_ema(tr.ema_decay if tr.use_ema else None)
         drop_on = tr._raw_model.training and tr._raw_model.dropout > 0
         self.drop_on = drop_on
@@ -400,8 +409,14 @@ class GraphedTrainStep:
                 if lt not in ("l1", "l2", "huber"):
                     raise ValueError(f"Unknown loss type: {lt}")
                 pred = pred.contiguous()
-                loss = K.loss_fwd(lt, pred, self.n_s)
-                dpred = K.loss_bwd(lt, pred, self.n_s, self.one)
+                if self.objective is None:
+                    loss = K.loss_fwd(lt, pred, self.n_s)
+                    dpred = K.loss_bwd(lt, pred, self.n_s, self.one)
+                else:
+                    # v target and / or min-SNR weights: loss and gradient from one pass over the static buffers
+                    ptype, sa, s1, w = self.objective
+                    loss, dpred = K.objective(ptype, lt, pred, self.x_s, self.n_s, self.t_s, sa, s1, w,
+                                              dloss=self.one)
                 ex.backward(tape, dpred, False)
                 del tape
                 _, coef = K.grad_norm_flat(ex.flat, 1.0)
@@ -546,6 +561,14 @@ class DiffusionTrainer:
         self.save_dir = Path(self.config.get('save_dir', './checkpoints'))
         self.sample_dir = Path(self.config.get('sample_dir', './generated_images'))
         self.loss_type = self.config.get('loss_type', 'l2')
+        # not in the reference: min-SNR-gamma loss weighting and the prediction type (diffusion/_objective.py); a
+        # 'prediction_type' key is applied to the diffusion object, without one the object's own value stands
+        self.snr_gamma = self.config.get('snr_gamma', None)
+        if self.snr_gamma is not None:
+            from ..diffusion._objective import check_gamma
+            self.snr_gamma = check_gamma(self.snr_gamma)
+        if self.config.get('prediction_type') is not None:
+            self.diffusion.set_prediction_type(self.config['prediction_type'])
         self.gradient_accumulation_steps = self.config.get('gradient_accumulation_steps', 1)
         self.save_interval = self.config.get('save_interval', 10)
         self.sample_interval = self.config.get('sample_interval', 5)
@@ -703,7 +726,9 @@ class DiffusionTrainer:
             loss = self._graph.step(images, t, labels_for_loss)
             if loss is not None:
                 return loss
-        loss = self.diffusion.p_losses(self.model, images, t, labels_for_loss, loss_type=self.loss_type)
+        # snr_gamma is passed only when set: a p_losses with the reference's signature keeps working
+        extra = {} if self.snr_gamma is None else {'snr_gamma': self.snr_gamma}
+        loss = self.diffusion.p_losses(self.model, images, t, labels_for_loss, loss_type=self.loss_type, **extra)
         loss = loss / self.gradient_accumulation_steps
         loss.backward()
         if (i + 1) % self.gradient_accumulation_steps == 0:

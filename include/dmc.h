@@ -31,6 +31,8 @@ enum { DMC_PRO_NONE = 0, DMC_PRO_AFFINE_SILU = 1, DMC_PRO_SILU = 2, DMC_PRO_AFFI
  * pro_groups = G, pro_eps = eps; no dropout. Only the whole-image small-map conv (4x4 / 8x8 maps) takes it:
  * dmc_conv_halo_prologue() says whether a descriptor can be run this way, dmc_conv2d fails otherwise. */
 enum { DMC_LOSS_L1 = 0, DMC_LOSS_L2 = 1, DMC_LOSS_HUBER = 2 };
+enum { DMC_PRED_EPS = 0, DMC_PRED_V = 1 };   /* what the network predicts: the noise, or v = alpha*eps - sigma*x0 */
+#define DMC_OBJECTIVE_MAX_BLOCKS 64          /* dmc_objective: partial sums per sample, at most */
 enum { DMC_PACK_FWD = 0, DMC_PACK_DGRAD = 1, DMC_PACK_UPDGRAD = 2 };
 
 int dmc_version(void);
@@ -309,6 +311,29 @@ int dmc_loss_fwd(int loss_type, const float* pred, const float* target, long n, 
                  float* workspace, void* stream);
 int dmc_loss_bwd(int loss_type, const float* pred, const float* target, long n, const float* dloss,
                  float* dpred, void* stream);
+/* Training objective with a prediction type and a per-sample weight, loss and gradient in ONE pass; not in the
+ * reference. v-prediction (Salimans & Ho 2022, arXiv:2202.00512): target = sa[t]*noise - s1[t]*x0 with
+ * sa = sqrt_alphas_cumprod, s1 = sqrt_one_minus_alphas_cumprod; DMC_PRED_EPS: target = noise (x0, sa, s1 unread).
+ * w: [T] per-timestep weight, e.g. min-SNR-gamma (Hang et al. 2023, arXiv:2303.09556; diffusion/_objective.py), or
+ * NULL for 1. pred, x0, noise: [N][per_sample] fp32; t: [N], clamped into [0, T).
+ *   loss[0] = (1/N) sum_n w[t_n] * (1/per_sample) * sum_i f(target - pred), f as dmc_loss_fwd; fixed order
+ *             (block partials per sample, samples in index order), no atomics: deterministic.
+ *   dpred   = df/dpred * (dloss[0] / (float)(N*per_sample)) * w[t_n]; NULL: forward only (dloss unread). With
+ *             DMC_PRED_EPS and w == NULL the bits of dmc_loss_bwd.
+ * Every mul/add/sub is a separate rounding. workspace: >= DMC_OBJECTIVE_MAX_BLOCKS * N floats. 16-byte accesses
+ * when per_sample % 4 == 0 and every pointer read or written is 16-byte aligned, element-wise otherwise. */
+int dmc_objective(int pred_type, int loss_type, const float* pred, const float* x0, const float* noise,
+                  const int64_t* t, const float* sa, const float* s1, const float* w, int T, int N,
+                  int per_sample, const float* dloss, float* loss, float* dpred, float* workspace,
+                  void* stream);
+/* v-prediction model output -> what the step kernels consume (arXiv:2202.00512 appendix D):
+ * eps = s1[t]*x + sa[t]*pred, x0 = sa[t]*x - s1[t]*pred (formed directly: no division by alpha). pred, eps_out,
+ * x0_out: [reps*N][per_sample]; row r*N + n pairs with x[n], t[n] (reps = 2: the batched cond / uncond forward of
+ * CFG). x0_out may be NULL. pred_type must be DMC_PRED_V: eps output needs no conversion and is refused. t is
+ * clamped into [0, T); access widths as dmc_objective. */
+int dmc_pred_convert(int pred_type, const float* x, const int64_t* t, const float* sa, const float* s1,
+                     int T, const float* pred, int reps, int N, int per_sample, float* eps_out,
+                     float* x0_out, void* stream);
 
 /* DDIM.p_sample update (diffusion/ddim.py:154-208), fused; alpha gathers on device; if any
  * t_next < 0 the reference uses alpha_next = 1 for the whole batch (:176-179), so does this.
