@@ -762,6 +762,7 @@ int check(int dtype, int ld_qkv, int heads, int hd, int ld_out) {
   DMC_REQUIRE(dtype == DMC_F32 || dtype == DMC_BF16, "attn: dtype");
   DMC_REQUIRE(hd > 0 && hd <= 64 && hd % kpl == 0, "attn: head dim %d must be <= 64 and a multiple of %d", hd, kpl);
   DMC_REQUIRE(ld_qkv % kpl == 0 && ld_out % kpl == 0 && ld_qkv >= 3 * heads * hd, "attn: pitch alignment");
+  DMC_REQUIRE(ld_out >= heads * hd, "attn: ld_out %d < heads * hd", ld_out);   // rows would overlap / run past the end
   return 0;
 }
 
@@ -787,7 +788,8 @@ extern "C" int dmc_attn_bwd(int dtype, const void* qkv, int ld_qkv, const void* 
                             uint32_t drop_seed, const uint32_t* drop_seed_base, uint32_t drop_thresh,
                             float drop_scale, void* stream) {
   if (check(dtype, ld_qkv, heads, hd, ld_out)) return 1;
-  DMC_REQUIRE(ld_dqkv >= 3 * heads * hd, "attn_bwd: ld_dqkv");
+  // the dQ / dK / dV rows are written as 4-element vectors: the pitch has to keep them aligned
+  DMC_REQUIRE(ld_dqkv >= 3 * heads * hd && ld_dqkv % 4 == 0, "attn_bwd: ld_dqkv");
   AttnK a{};
   a.qkv = (const char*)qkv; a.ld_qkv = ld_qkv; a.o = (const char*)out; a.dout = (const char*)dout; a.ld_o = ld_out;
   a.lse = lse; a.out = (char*)dqkv; a.ld_out = ld_dqkv;
