@@ -113,13 +113,52 @@ class _PackCache:
 
 
 class ExecCore:
-    """What every backbone executor shares: weight packing through the pack cache, the generic implicit-GEMM conv
-    / weight-gradient launchers over 1-2 NHWC sources, activation allocation and views of the flat gradient
-    buffer. Subclasses set self.dt, self.packs, self.device, self.training_grad_scale, self.pindex, self.goff, and
-    bind their model with _bind_model."""
+    """What every backbone executor shares: the executor state (_setup), weight packing through the pack cache, the
+    generic implicit-GEMM conv / weight-gradient launchers over 1-2 NHWC sources, activation allocation, the flat
+    gradient buffer with its layout and views, and run() behind the one autograd Function. A subclass calls _setup
+    and _set_grad_order in its __init__, sets self.device in forward(x, t, y, keep) -> (out, tape) and takes the
+    buffer of its backward(tape, dout, x_requires_grad) -> (dx, grads) from _grad_buffer."""
 
-    def _bind_model(self, model):
-        self._mref = weakref.ref(model)
+    def _setup(self, model):
+        self._mref = weakref.ref(model)     # see m
+        self.dt = model.compute_dtype
+        self.cdt = L.dtype_code(self.dt)
+        self.chunk = L.chunk_for(self.dt)
+        self.wgen = 0               # weight generation: bumped when a fused step rewrote the parameters
+        self.packs = _PackCache(self)
+        self.params = list(model.parameters())
+        self.pindex = {id(p): i for i, p in enumerate(self.params)}
+        self.training_grad_scale = 1.0
+        self.grad_hook = None       # called as hook(flat_grad, hi, last) when the prefix [0, hi) of the grads is final
+        self.seed_ptr = None        # device address of the dropout seed word (graph-captured training step)
+
+    def _set_grad_order(self, order):
+        """Lay the flat fp32 gradient buffer out in `order` (every parameter exactly once): goff[i] is the offset of
+        params[i], gtotal the length."""
+        assert len(order) == len(self.params) and {id(p) for p in order} == set(self.pindex), "gradient layout"
+        self.goff = [0] * len(self.params)
+        off = 0
+        for p in order:
+            self.goff[self.pindex[id(p)]] = off
+            off += p.numel()
+        self.gtotal = off
+
+    def _grad_buffer(self, device):
+        # The flat gradient buffer is reused across steps when no parameter still holds a gradient view of
+        # it (optimizer.zero_grad(set_to_none=True)); with gradient accumulation a fresh one is used.
+        flat = getattr(self, "_flat", None)
+        if flat is None or flat.device != device or any(p.grad is not None for p in self.params):
+            flat = torch.empty(self.gtotal, dtype=torch.float32, device=device)
+        self._flat = flat
+        self.flat = flat
+        return flat
+
+    def run(self, x, t, y=None):
+        need_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.params))
+        if need_grad:
+            return _ExecFunction.apply(self, x, t, y, *self.params)
+        out, _ = self.forward(x, t, y, keep=False)
+        return out
 
     @property
     def m(self):
@@ -229,16 +268,9 @@ class ExecCore:
 
 class UNetExecutor(ExecCore):
     def __init__(self, model):
-        self._bind_model(model)
-        self.dt = model.compute_dtype
-        self.cdt = L.dtype_code(self.dt)
-        self.chunk = L.chunk_for(self.dt)
+        self._setup(model)
         self._halo_pro_cache = {}   # shape -> dmc_conv_halo_prologue verdict
         self._gsa_cache = {}        # shape -> dmc_gn_stats_apply_ok verdict
-        self.wgen = 0               # weight generation: bumped when a fused step rewrote the parameters
-        self.packs = _PackCache(self)
-        self.params = list(model.parameters())
-        self.pindex = {id(p): i for i, p in enumerate(self.params)}
         # time-embedding projection layout: all ResidualBlocks' time_mlp (and label_proj) rows side by side
         self.res_blocks = [mod for mod in model.modules() if type(mod).__name__ == "ResidualBlock"]
         self.temb_off = {}
@@ -249,9 +281,6 @@ class UNetExecutor(ExecCore):
         self.temb_total = off
         self._layout_grads()
         self.daddvec = None
-        self.training_grad_scale = 1.0
-        self.grad_hook = None       # called as hook(flat_grad, lo, hi) when a range of grads is final
-        self.seed_ptr = None        # device address of the dropout seed word (graph-captured training step)
         # the layer sequence of UNet.forward (models/unet.py:270-289): (layer, takes the [h, skip] concat, pushes a
         # skip) -- walked with one step of lookahead so each conv knows which GroupNorm reads its output next
         self.plan = []
@@ -284,13 +313,7 @@ class UNetExecutor(ExecCore):
         last = list(m.input_conv.parameters())
         tail_ids = {id(p) for p in tail + last}
         head = [p for p in reversed(self.params) if id(p) not in tail_ids]
-        order = head + tail + last
-        self.goff = [0] * len(self.params)
-        off = 0
-        for p in order:
-            self.goff[self.pindex[id(p)]] = off
-            off += p.numel()
-        self.gtotal = off
+        self._set_grad_order(head + tail + last)
         self.temb_w_off = self.goff[self.pindex[id(tail[0])]]
         self.temb_b_off = self.goff[self.pindex[id(tail[len(rbs)])]]
         self.temb_l_off = self.goff[self.pindex[id(tail[2 * len(rbs)])]] if m.num_classes is not None else None
@@ -447,14 +470,6 @@ class UNetExecutor(ExecCore):
         return act.grad, 1
 
     # =========================================================================================
-    def run(self, x, t, y=None):
-        params = self.params
-        need_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
-        if need_grad:
-            return _UNetFunction.apply(self, x, t, y, *params)
-        out, _ = self.forward(x, t, y, keep=False)
-        return out
-
     def forward(self, x, t, y, keep):
         m = self.m
         self.device = x.device
@@ -653,13 +668,7 @@ class UNetExecutor(ExecCore):
 
     # =========================================================================================
     def backward(self, tape, dout, x_requires_grad):
-        # The flat gradient buffer is reused across steps when no parameter still holds a gradient view of
-        # it (optimizer.zero_grad(set_to_none=True)); with gradient accumulation a fresh one is used.
-        flat = getattr(self, "_flat", None)
-        if flat is None or flat.device != dout.device or any(p.grad is not None for p in self.params):
-            flat = torch.empty(self.gtotal, dtype=torch.float32, device=dout.device)
-        self._flat = flat
-        self.flat = flat
+        flat = self._grad_buffer(dout.device)
         self.daddvec = None
         self._dx = None
         gv = lambda p: self._gview(flat, p)  # noqa: E731
@@ -967,7 +976,10 @@ class UNetExecutor(ExecCore):
         self._wgrad([A0], de1, tdim, K.TAPS1, 1, 1, tdim, gv(te[1].weight), dtype=f32, dbias=gv(te[1].bias))
 
 
-class _UNetFunction(torch.autograd.Function):
+class _ExecFunction(torch.autograd.Function):
+    """ExecCore.run under autograd: the executor's forward keeps its tape, its backward returns the views of the flat
+    gradient buffer."""
+
     @staticmethod
     def forward(ctx, ex, x, t, y, *params):
         out, tape = ex.forward(x, t, y, keep=True)
