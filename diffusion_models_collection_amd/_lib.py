@@ -45,6 +45,17 @@ class ConvDesc(ctypes.Structure):
     ]
 
 
+class ConvPlan(ctypes.Structure):
+    """include/dmc.h dmc_conv_plan"""
+    _fields_ = [("family", _c_int), ("grid", ctypes.c_uint * 3), ("block", _c_int), ("splits", _c_int),
+                ("gn_part", _c_int), ("fused_prologue", _c_int), ("ws_bytes", _c_size)]
+
+
+# include/dmc.h DMC_CONV_* (by code) and DMC_GN_PART_*
+CONV_FAMILIES = ("none", "nin_halo", "nout_halo", "narrow_in", "narrow_out", "img", "gemm1x1", "halo", "glds", "reg")
+GN_PART_NONE, GN_PART_KERNEL, GN_PART_SPLITK, GN_PART_PASS = 0, 1, 2, 3
+
+
 class WgradJob(ctypes.Structure):
     """include/dmc.h dmc_wgrad_job"""
     _fields_ = [("slab", ctypes.c_void_p), ("bslab", ctypes.c_void_p), ("dw", ctypes.c_void_p),
@@ -94,6 +105,7 @@ def _load():
         "dmc_conv2d_workspace": (_c_size, [ctypes.POINTER(ConvDesc)]),
         "dmc_conv_halo_prologue": (_c_int, [ctypes.POINTER(ConvDesc)]),
         "dmc_conv2d_fused_epilogue": (_c_int, [ctypes.POINTER(ConvDesc), ctypes.c_size_t]),
+        "dmc_conv2d_plan": (_c_int, [ctypes.POINTER(ConvDesc), ctypes.c_size_t, ctypes.POINTER(ConvPlan)]),
         "dmc_conv2d": (_c_int, [ctypes.POINTER(ConvDesc), _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_size, _c_p]),
         "dmc_conv2d_wgrad_workspace": (_c_size, [ctypes.POINTER(ConvDesc)]),
         "dmc_conv2d_wgrad": (_c_int, [ctypes.POINTER(ConvDesc), _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_f, _c_p]),

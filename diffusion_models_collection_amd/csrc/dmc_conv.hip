@@ -1547,25 +1547,27 @@ __global__ __launch_bounds__(256) void conv3x3_img_kernel(ConvK a) {
     for (int j = 0; j < NJ; ++j) conv_store_tile<T>(a, acc[i][j], m0 + qrow[j], n0 + i * 16 + fh * 4);
 }
 
+// Operands the LDS-DMA kernels can fetch by buffer loads: whole 64-channel planes with no K padding, and extents
+// that fit a buffer resource.
+bool dma_operands_ok(const ConvK& k) {
+  return k.C1 % 64 == 0 && k.C2 % 64 == 0 && k.Kc == k.C1 + k.C2 && k.x1_bytes > 0 && (k.C2 == 0 || k.x2_bytes > 0) &&
+         k.w_bytes > 0;
+}
+
 // The whole-image small-map kernel applies (bf16 3x3 stride 1 on 4x4 / 8x8 maps, 64-aligned sources, no prologue,
 // DMC_IMG_MASK bit set for the shape: bit 0 4x4 forward, 1 4x4 input gradient, 2 8x8 forward, 3 8x8 input
 // gradient; default 15): returns its channel tile BN (16 or 32), or 0. Same-box A/B of the B = 128 bench
 // (two interleaved runs): mask 0 train 10,481 / 10,458, DDIM-50 728 / 728; mask 3 (4x4) 10,696 / 10,678, 759 / 760;
 // mask 7 10,793 / 10,800, 781 / 788; mask 15 10,797 / 10,813, 780 / 783.
-int img_plan(const ConvK& k) {
-  const long mask = dmc::opt(dmc::OPT_IMG_MASK);
+int img_plan(const ConvK& k, long mask) {
   if (!mask || k.dtype_bytes != 2 || (k.prologue != DMC_PRO_NONE && k.prologue != DMC_PRO_GN_SILU)) return 0;
   if (k.prologue == DMC_PRO_GN_SILU) {   // forward convs of SiLU(GroupNorm(x)) with whole groups in a 64-channel chunk
     const int C = k.C1 + k.C2;
     if (k.tdy0 != -1 || C > 512 || k.gn_G <= 0 || C % k.gn_G || (C / k.gn_G) % 8 || 64 % (C / k.gn_G) || k.dthresh)
       return 0;
   }
-  if (k.mode != DMC_MODE_NORMAL || k.stride != 1 || k.ntaps != 9 || k.tkw != 3) return 0;
-  if (!((k.tdy0 == -1 && k.tsy == 1) || (k.tdy0 == 1 && k.tsy == -1))) return 0;
-  if (!((k.tdx0 == -1 && k.tsx == 1) || (k.tdx0 == 1 && k.tsx == -1))) return 0;
-  if (k.OH != k.H || k.OW != k.W || !((k.OH == 8 && k.OW == 8) || (k.OH == 4 && k.OW == 4)) || k.M % 128) return 0;
-  if (k.C1 % 64 || k.C2 % 64 || k.Kc != k.C1 + k.C2 || k.x1_bytes == 0 || (k.C2 && k.x2_bytes == 0) || k.w_bytes == 0)
-    return 0;
+  if (!same_size_3x3(k) || !((k.OH == 8 && k.OW == 8) || (k.OH == 4 && k.OW == 4)) || k.M % 128) return 0;
+  if (!dma_operands_ok(k)) return 0;
   const int bit = (k.OH == 8 ? 2 : 0) + (k.tdy0 == 1 ? 1 : 0);
   if (!((mask >> bit) & 1)) return 0;
   // 256-pixel tiles (4 images) at 8x8, 128 (8 images) at 4x4; the channel tile (16 / 32) that gives ~256 blocks
@@ -1581,36 +1583,19 @@ int img_plan(const ConvK& k) {
   return bn;
 }
 
-void launch_img(const ConvK& k, int bn, hipStream_t s) {
-  const int bm = k.OH == 8 ? 256 : 128;
-  const dim3 g(k.M / bm * (k.Cout / bn));
-  if (k.prologue == DMC_PRO_GN_SILU) {
-    if (bm == 256) conv3x3_img_kernel<32, 64, 2, true><<<g, 256, 0, s>>>(k);
-    else conv3x3_img_kernel<16, 32, 4, true><<<g, 256, 0, s>>>(k);
-    return;
-  }
-  if (bm == 256) {
-    if (bn == 16) conv3x3_img_kernel<16, 64, 3><<<g, 256, 0, s>>>(k);
-    else conv3x3_img_kernel<32, 64, 2><<<g, 256, 0, s>>>(k);
-  } else {
-    if (bn == 16) conv3x3_img_kernel<16, 32, 4><<<g, 256, 0, s>>>(k);
-    else conv3x3_img_kernel<32, 32, 3><<<g, 256, 0, s>>>(k);
-  }
-}
-
 // The halo'd narrow kernels (conv3x3_nin_kernel / conv3x3_nout_kernel, below): bf16, 3x3 stride 1 on halo2_plan's
 // 128-pixel geometry. nin: one source of <= 8 channels (one chunk per pixel), Cout a multiple of 128. nout: Cout <=
-// 16, 64-aligned sources of <= 128 channels in all. Return the halo pieces per wave (6/7/9), or 0.
+// 8 (plan_conv asks only then), 64-aligned sources of <= 128 channels in all. Return the halo pieces per wave
+// (6/7/9), or 0.
 int nin_plan(const ConvK& k, int* R, int* nimg) {
-  if (dmc::opt(dmc::OPT_NO_NHALO) || k.dtype_bytes != 2 || k.prologue != DMC_PRO_NONE || k.C2 != 0 || k.C1 > 8 ||
-      k.ld1 != 8 || k.Cout % 128 || k.silu_pre || k.act)
+  if (k.dtype_bytes != 2 || k.prologue != DMC_PRO_NONE || k.C2 != 0 || k.C1 > 8 || k.ld1 != 8 || k.Cout % 128 ||
+      k.silu_pre || k.act)
     return 0;
   return halo2_plan(k, R, nimg);
 }
 int nout_plan(const ConvK& k, int* R, int* nimg) {
-  if (dmc::opt(dmc::OPT_NO_NHALO) || k.dtype_bytes != 2 || k.prologue != DMC_PRO_NONE || k.Cout > 16 ||
-      k.C1 % 64 || k.C2 % 64 || k.C1 + k.C2 > 128 || k.Kc != k.C1 + k.C2 || k.x1_bytes == 0 ||
-      (k.C2 && k.x2_bytes == 0) || k.w_bytes == 0 || k.act)
+  if (k.dtype_bytes != 2 || k.prologue != DMC_PRO_NONE || k.Cout > 16 || k.C1 + k.C2 > 128 || !dma_operands_ok(k) ||
+      k.act)
     return 0;
   return halo2_plan(k, R, nimg);
 }
@@ -2256,67 +2241,6 @@ RegPlan plan_reg(const ConvK& k) {
   return p;
 }
 
-// Halo kernel with the GN-affine+SiLU prologue applied to the resident halo (inference: no dropout, the
-// normalised activation is not needed for a weight gradient). Returns the DMA pieces (6/7/9) or 0.
-int halo2_pro_plan(const ConvK& k, int* R, int* nimg) {
-  if (k.dtype_bytes != 2 || k.prologue != DMC_PRO_AFFINE_SILU || k.dthresh != 0 || k.ldp < k.C1 + k.C2) return 0;
-  // default since round 2 (DMC_HALO_PRO=0 turns it off): with the GroupNorm statistics taken from the producing
-  // conv's epilogue the activation is not read at all before this conv; DDIM-50 645 -> 658 img/s, CFG 379 -> 389
-  // (round 1, with a statistics pass still in front of it, it was neutral: the halo rewrite costs ~17 % conv time)
-  if (!dmc::opt(dmc::OPT_HALO_PRO) || dmc::opt(dmc::OPT_NO_HALO) || dmc::opt(dmc::OPT_NO_GLDS) ||
-      dmc::opt(dmc::OPT_NO_BUFLDS))
-    return 0;
-  const bool buf = k.C1 % 64 == 0 && k.C2 % 64 == 0 && k.Kc == k.C1 + k.C2 && k.x1_bytes > 0 &&
-                   (k.C2 == 0 || k.x2_bytes > 0) && k.w_bytes > 0;
-  // small problems keep the split-K GEMM (fed by a materialised GroupNorm output)
-  if (!buf || (plan_glds(k).splits != 1 && !dmc::opt(dmc::OPT_NO_SPLITK))) return 0;
-  const int hp = halo2_plan(k, R, nimg);
-  return *nimg == 1 ? hp : 0;   // one image per tile: a lane's scale/shift row is the same in every piece
-}
-
-template <bool PRO>
-void launch_halo2(const ConvK& k, int hp, int R, int nimg, hipStream_t s) {
-  const dim3 g = dmc::opt(dmc::OPT_NO_XCD) ? dim3(k.M / 128, dmc::cdiv(k.Cout, 128))
-                                          : dim3(k.M / 128 * dmc::cdiv(k.Cout, 128));
-  if (hp == 6) conv3x3_halo2_kernel<6, 3, PRO><<<g, 256, 0, s>>>(k, R, nimg);
-  else if (hp == 7) conv3x3_halo2_kernel<7, 3, PRO><<<g, 256, 0, s>>>(k, R, nimg);
-  else conv3x3_halo2_kernel<9, 2, PRO><<<g, 256, 0, s>>>(k, R, nimg);
-}
-
-template <bool BUF>
-void launch_glds(ConvK k, const FwdPlan& p, hipStream_t s) {
-  if (p.splits > 1) {
-    const dim3 gs(dmc::cdiv(k.M, 128), dmc::cdiv(k.Cout, 128), p.splits);
-    // (a 2-stage ring with two split blocks per CU and deeper 4 / 5-stage rings measured neutral or slower, round 4)
-    conv_fwd_glds_kernel<2, 2, BUF><<<gs, 256, 0, s>>>(k);
-    const int Cpad = dmc::cdiv(k.Cout, 128) * 128;
-    if (k.gsk && k.M % 64 == 0 && k.Cout % 8 == 0 && !k.out_f32 && !k.out_nchw && k.Csplit == k.Cout) {
-      launch_splitk_epi_gn(k, p.splits, Cpad, s);
-      if (k.gsk_done) *k.gsk_done = 1;
-      return;
-    }
-    const long total = (long)k.M * Cpad / 4;
-    const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    launch_splitk_epilogue<bf16_t>(k, p.splits, Cpad, blocks, s);
-  } else {
-    // 1-D grid: the kernel orders its tiles XCD-aware (xcd_tile); DMC_NO_XCD=1 keeps the 2-D grid (A/B)
-    const int bm = p.cfg == 0 ? 256 : p.cfg == 1 ? 128 : 64;
-    const int nb = dmc::cdiv(k.Cout, 128);
-    const dim3 g = dmc::opt(dmc::OPT_NO_XCD) ? dim3(dmc::cdiv(k.M, bm), nb) : dim3(dmc::cdiv(k.M, bm) * nb);
-    if (p.cfg == 0) {
-      // 128x128 tiles, 2-stage ring, two blocks per CU (the 8-wave 256x128 tile with a 3-stage ring, one block per
-      // CU, measured slower: round 2)
-      const dim3 g2 = dmc::opt(dmc::OPT_NO_XCD) ? dim3(dmc::cdiv(k.M, 128), nb) : dim3(dmc::cdiv(k.M, 128) * nb);
-      conv_fwd_glds_kernel<2, 2, BUF, 2><<<g2, 256, 0, s>>>(k);
-    } else if (p.cfg == 1 && (long)dmc::cdiv(k.M, 128) * nb > 256)
-      // more 128x128 tiles than CUs: the 2-stage ring fits two blocks per CU (one round instead of two; the
-      // 8x8 attention qkv GEMM: 384 tiles)
-      conv_fwd_glds_kernel<2, 2, BUF, 2><<<g, 256, 0, s>>>(k);
-    else if (p.cfg == 1) conv_fwd_glds_kernel<2, 2, BUF><<<g, 256, 0, s>>>(k);
-    else conv_fwd_glds_kernel<1, 2, BUF><<<g, 128, 0, s>>>(k);
-  }
-}
-
 // GroupNorm partials of a stored NHWC output, for the conv paths whose epilogue does not emit them (fp32, split-K,
 // narrow, register-staged): one wave per (64-pixel segment, 8-channel chunk), (mean, M2) by an exact two-pass.
 template <typename T>
@@ -2340,44 +2264,14 @@ __global__ __launch_bounds__(256) void gn_part_kernel(const char* y, int ldy, in
   if (lane == 0) { out[w * 2] = m; out[w * 2 + 1] = q; }
 }
 
-// Whether dmc_conv2d's chosen kernel emits the GroupNorm partials in its epilogue (tile_epilogue8: bf16, one NHWC
-// output, 128-channel tiles, 64-pixel partial segments). The kernels that can: conv3x3_halo2_kernel (128-pixel
-// tiles, with or without the halo prologue) and the non-split LDS-DMA kernel (128- or 256-pixel tiles). M % 256 is
-// kept on purpose: it is what the 256-pixel LDS-DMA tile needs, and every UNet shape that reaches here meets it
-// (B * OH * OW with OH * OW >= 64 and B even), so one condition serves both kernels.
-bool epi_stats_ok(const ConvK& k, const void* ws, size_t ws_bytes) {
-  if (k.dtype_bytes != 2 || k.out_f32 || k.out_nchw || k.silu_pre || k.Csplit != k.Cout || k.Cout % 128 ||
-      k.M % 256 || k.OHW % 64 || ((k.Cout | k.ldy1 | k.ld_res) & 7))
-    return false;
-  if (!dmc::opt(dmc::OPT_NO_NARROW) && ((k.C2 == 0 && k.C1 <= 8 && k.Cout >= 16) || k.Cout <= 8)) {
-    int R, nimg;   // the halo'd narrow-input kernel runs the shared LDS epilogue (128-channel tiles)
-    return nin_plan(k, &R, &nimg) != 0;
-  }
-  if (dmc::opt(dmc::OPT_NO_GLDS) || dmc::opt(dmc::OPT_NO_EPI_STATS))
-    return false;
-  if (img_plan(k))   // conv3x3_img_kernel: partials from its plain-epilogue 64-pixel waves (8x8 maps) only
-    return k.OH == 8 && k.act == DMC_ACT_NONE;
-  if (k.prologue == DMC_PRO_AFFINE_SILU) {
-    int R, nimg;
-    return halo2_pro_plan(k, &R, &nimg) != 0;
-  }
-  if (k.prologue != DMC_PRO_NONE) return false;
-  const FwdPlan p = plan_glds(k);
-  return p.splits == 1 || ws == nullptr || ws_bytes < p.ws || dmc::opt(dmc::OPT_NO_SPLITK);
-}
-
-
 // The persistent 1x1 GEMM applies (bf16 1x1 stride-1, 64-aligned channel sources, plain bias epilogue, whole
 // 128x128 tiles, enough tiles to give every CU one block): returns the tiles per block, or 0.
 int gemm1x1_plan(const ConvK& k) {
-  if (!dmc::opt(dmc::OPT_GEMM1X1) || k.dtype_bytes != 2 || k.ntaps != 1 || k.stride != 1 || k.mode != DMC_MODE_NORMAL ||
-      k.tdy0 || k.tdx0 || k.H != k.OH || k.W != k.OW || k.prologue != DMC_PRO_NONE)
+  if (k.dtype_bytes != 2 || k.ntaps != 1 || k.stride != 1 || k.mode != DMC_MODE_NORMAL || k.tdy0 || k.tdx0 ||
+      k.H != k.OH || k.W != k.OW || k.prologue != DMC_PRO_NONE || !dma_operands_ok(k))
     return 0;
-  if (k.C1 % 64 || k.C2 % 64 || k.Kc != k.C1 + k.C2 || k.x1_bytes == 0 || (k.C2 && k.x2_bytes == 0) || k.w_bytes == 0)
-    return 0;
-  if (k.addvec || (k.resid && (k.ld_res & 3)) || k.silu_pre || k.gst || k.gsk ||
-      k.act != DMC_ACT_NONE || k.sk || k.out_f32 || k.out_nchw || (k.ldy1 & 3) || k.M % 128 ||
-      k.Cout % 128 || k.Cout > 1024)
+  if (k.addvec || (k.resid && (k.ld_res & 3)) || k.silu_pre || k.act != DMC_ACT_NONE || k.out_f32 || k.out_nchw ||
+      (k.ldy1 & 3) || k.M % 128 || k.Cout % 128 || k.Cout > 1024)
     return 0;
   // a split output: whole 128-channel tiles on each side, no residual (the accumulate form is single-output)
   if (k.Csplit != k.Cout && (k.Csplit % 128 || (k.ldy2 & 3) || !k.y2 || k.resid)) return 0;
@@ -2387,140 +2281,308 @@ int gemm1x1_plan(const ConvK& k) {
   return (int)((ntiles + blocks - 1) / blocks);
 }
 
-template <typename T>
-int launch_fwd(ConvK k, void* ws, size_t ws_bytes, hipStream_t s) {
-  constexpr int EPC = TT<T>::KPL;
-  DMC_REQUIRE(k.prologue != DMC_PRO_GN_SILU || img_plan(k),
-              "conv: DMC_PRO_GN_SILU is taken only by the small-map conv (dmc_conv_halo_prologue says when)");
-  if (!dmc::opt(dmc::OPT_NO_NARROW) && sizeof(T) == 2) {
-    int R, nimg;
-    if (k.C2 == 0 && k.C1 <= EPC && k.Cout >= 16 && nin_plan(k, &R, &nimg)) {
-      if (reg_epi_ok(k)) conv3x3_nin_kernel<true><<<dim3(k.M / 128, k.Cout / 128), 256, 0, s>>>(k, R, nimg);
-      else conv3x3_nin_kernel<false><<<dim3(k.M / 128, k.Cout / 128), 256, 0, s>>>(k, R, nimg);
-      return dmc::check_launch("dmc_conv2d");
-    }
-    const int hp = k.Cout <= 8 ? nout_plan(k, &R, &nimg) : 0;
-    if (hp) {
-      const int npl = (k.C1 + k.C2) / 64;
-      const dim3 g(k.M / 128);
-      if (hp == 6) { if (npl == 1) conv3x3_nout_kernel<6, 1><<<g, 256, 0, s>>>(k, R, nimg); else conv3x3_nout_kernel<6, 2><<<g, 256, 0, s>>>(k, R, nimg); }
-      else if (hp == 7) { if (npl == 1) conv3x3_nout_kernel<7, 1><<<g, 256, 0, s>>>(k, R, nimg); else conv3x3_nout_kernel<7, 2><<<g, 256, 0, s>>>(k, R, nimg); }
-      else { if (npl == 1) conv3x3_nout_kernel<9, 1><<<g, 256, 0, s>>>(k, R, nimg); else conv3x3_nout_kernel<9, 2><<<g, 256, 0, s>>>(k, R, nimg); }
-      return dmc::check_launch("dmc_conv2d");
-    }
+// Everything dmc_conv2d decides before it launches, decided once: launch_conv runs it, the queries
+// (dmc_conv2d_workspace, dmc_conv2d_fused_epilogue, dmc_conv_halo_prologue, dmc_conv2d_plan) report it.
+struct ConvPlan {
+  int family = DMC_CONV_NONE;
+  dim3 grid{0, 0, 0};           // of the main launch
+  int block = 256;
+  int hp = 0, R = 0, nimg = 0;  // halo geometry (halo and halo'd narrow kernels): pieces per wave, rows, images per tile
+  int npl = 0;                  // halo'd narrow-out: 64-channel source planes
+  int bn = 0;                   // small-map: channel tile
+  int tpb = 0;                  // persistent GEMM: tiles per block
+  int wm = 2, stages = 3;       // LDS-DMA: 64-pixel wave rows per tile (2: 128 pixels, 1: 64) and ring depth
+  bool buf = false;             // LDS-DMA: buffer-resource (true) or plain (false) operand addressing
+  int tile = 64;                // register-staged: 128x128 or 64x64 tiles
+  int splits = 1, per = 0;      // split-K over grid.z: splits, K stages per split
+  bool fused_pro = false;       // the GroupNorm prologue runs on the kernel's resident tile (dmc_conv_halo_prologue)
+  int gn = DMC_GN_PART_NONE;    // who writes the GroupNorm partials
+  size_t ws_report = 0;         // what dmc_conv2d_workspace answers
+};
+
+// The dispatch order and what each family requires are listed in DESIGN.md ("Forward conv dispatch"), with the
+// inherited quirks this function keeps on purpose. want_gn_part: the caller asked for the GroupNorm partials;
+// ws_avail: bytes of workspace the launch will get (0: none).
+ConvPlan plan_conv(const ConvK& k, bool want_gn_part, size_t ws_avail) {
+  ConvPlan p;
+  if (k.M == 0 || k.Cout == 0) return p;
+  const bool bf16 = k.dtype_bytes == 2;
+  const int epc = bf16 ? 8 : 4;
+  const bool no_splitk = dmc::opt(dmc::OPT_NO_SPLITK), no_glds = dmc::opt(dmc::OPT_NO_GLDS);
+  const bool no_halo = dmc::opt(dmc::OPT_NO_HALO), no_xcd = dmc::opt(dmc::OPT_NO_XCD);
+  const bool dma = dma_operands_ok(k), buf = dma && !dmc::opt(dmc::OPT_NO_BUFLDS);
+  const int nb128 = dmc::cdiv(k.Cout, 128);
+  auto tiles = [&](int bm) {   // the LDS-DMA / halo grid: 1-D (XCD-aware tile order in the kernel) unless DMC_NO_XCD
+    return no_xcd ? dim3(dmc::cdiv(k.M, bm), nb128) : dim3(dmc::cdiv(k.M, bm) * nb128);
+  };
+
+  // the split-K helper plans, each at most once
+  const bool glds_path = bf16 && k.prologue == DMC_PRO_NONE && !no_glds;
+  const bool pro_cand = bf16 && k.prologue == DMC_PRO_AFFINE_SILU && k.dthresh == 0 && k.ldp >= k.C1 + k.C2 &&
+                        dmc::opt(dmc::OPT_HALO_PRO) && !no_halo && !no_glds && buf;
+  const FwdPlan gp = (glds_path || pro_cand) ? plan_glds(k) : FwdPlan{0, 1, 0, 0};
+  const RegPlan rp = glds_path ? RegPlan{false, 1, 0, 0} : plan_reg(k);
+  p.ws_report = glds_path ? gp.ws : rp.ws;
+
+  // candidate forms (pure predicates of the descriptor and the options)
+  const bool narrow = !dmc::opt(dmc::OPT_NO_NARROW), nhalo = narrow && bf16 && !dmc::opt(dmc::OPT_NO_NHALO);
+  const bool narrow_in = narrow && k.C2 == 0 && k.C1 <= epc && k.Cout >= 16;
+  int R = 0, nimg = 0;
+  const int nin_hp = nhalo && narrow_in ? nin_plan(k, &R, &nimg) : 0;
+  const int img_bn = img_plan(k, dmc::opt(dmc::OPT_IMG_MASK));
+  // the halo kernel with the GN-affine+SiLU prologue on its resident halo (inference: no dropout); small problems
+  // keep the split-K GEMM fed by a materialised GroupNorm output; one image per tile: a lane's scale / shift row is
+  // the same in every piece
+  int pro_R = 0, pro_nimg = 0;
+  int pro_hp = pro_cand && (gp.splits == 1 || no_splitk) ? halo2_plan(k, &pro_R, &pro_nimg) : 0;
+  if (pro_nimg != 1) pro_hp = 0;
+  p.fused_pro = pro_hp != 0 || (k.prologue == DMC_PRO_GN_SILU && img_bn != 0);
+
+  // Does the kernel that will run emit the GroupNorm partials in its epilogue (tile_epilogue8 / reg_epilogue: bf16,
+  // one NHWC output, 128-channel tiles, 64-pixel segments)? M % 256 is kept on purpose: it is what the 256-pixel
+  // LDS-DMA tile needs, and every UNet shape that reaches here meets it.
+  bool epi = false;
+  if (want_gn_part && bf16 && !k.out_f32 && !k.out_nchw && !k.silu_pre && k.Csplit == k.Cout && k.Cout % 128 == 0 &&
+      k.M % 256 == 0 && k.OHW % 64 == 0 && !((k.Cout | k.ldy1 | k.ld_res) & 7)) {
+    if (narrow_in) epi = nin_hp != 0;   // the halo'd narrow-input kernel runs the shared epilogue
+    else if (no_glds || dmc::opt(dmc::OPT_NO_EPI_STATS)) epi = false;
+    else if (img_bn) epi = k.OH == 8 && k.act == DMC_ACT_NONE;   // its plain-epilogue 64-pixel waves (8x8 maps) only
+    else if (k.prologue == DMC_PRO_AFFINE_SILU) epi = pro_hp != 0;
+    else if (k.prologue == DMC_PRO_NONE) epi = gp.splits == 1 || ws_avail < gp.ws || no_splitk;
   }
-  if (!dmc::opt(dmc::OPT_NO_NARROW)) {
-    if (k.C2 == 0 && k.C1 <= EPC && k.Cout >= 16) {
-      conv_narrow_in_kernel<T><<<dim3(dmc::cdiv(k.M, 256), dmc::cdiv(k.Cout, 32)), 256, 0, s>>>(k);
-      return dmc::check_launch("dmc_conv2d");
+  // otherwise the split-K epilogue emits them where one runs (DMC_NO_SKGN=1: never), else a pass over the output
+  const bool skgn = want_gn_part && !epi && !dmc::opt(dmc::OPT_NO_SKGN);
+  p.gn = !want_gn_part ? DMC_GN_PART_NONE : epi ? DMC_GN_PART_KERNEL : DMC_GN_PART_PASS;
+
+  if (nin_hp) {
+    p.family = DMC_CONV_NIN_HALO; p.hp = nin_hp; p.R = R; p.nimg = nimg;
+    p.grid = dim3(k.M / 128, k.Cout / 128);
+    return p;
+  }
+  if (nhalo && k.Cout <= 8 && (p.hp = nout_plan(k, &p.R, &p.nimg)) != 0) {
+    p.family = DMC_CONV_NOUT_HALO; p.npl = (k.C1 + k.C2) / 64;
+    p.grid = dim3(k.M / 128);
+    return p;
+  }
+  if (narrow_in) {
+    p.family = DMC_CONV_NARROW_IN;
+    p.grid = dim3(dmc::cdiv(k.M, 256), dmc::cdiv(k.Cout, 32));
+    return p;
+  }
+  if (narrow && k.Cout <= 8 && (k.C2 == 0 || k.C1 % epc == 0)) {
+    p.family = DMC_CONV_NARROW_OUT;
+    p.grid = dim3(dmc::cdiv(k.M, 256));
+    return p;
+  }
+  if (img_bn) {
+    p.family = DMC_CONV_IMG; p.bn = img_bn;
+    p.grid = dim3(k.M / (k.OH == 8 ? 256 : 128) * (k.Cout / img_bn));
+    return p;
+  }
+  // a conv asked for partials stays off the persistent GEMM (which has no such epilogue) while either epilogue
+  // form is armed
+  if (dmc::opt(dmc::OPT_GEMM1X1) && !epi && !skgn && (p.tpb = gemm1x1_plan(k)) != 0) {
+    p.family = DMC_CONV_GEMM1X1;
+    p.grid = dim3(dmc::cdiv((k.M / 128) * (k.Cout / 128), p.tpb));
+    return p;
+  }
+  if (pro_hp) {
+    p.family = DMC_CONV_HALO; p.hp = pro_hp; p.R = pro_R; p.nimg = pro_nimg;
+    p.grid = tiles(128);
+    return p;
+  }
+  if (glds_path) {
+    const bool split = gp.splits > 1 && ws_avail >= gp.ws && !no_splitk;
+    p.buf = buf;
+    if (buf && !split && !no_halo && (p.hp = halo2_plan(k, &p.R, &p.nimg)) != 0) {
+      p.family = DMC_CONV_HALO;
+      p.grid = tiles(128);
+      return p;
     }
-    if (k.Cout <= 8 && (k.C2 == 0 || k.C1 % EPC == 0)) {
-      conv_narrow_out_kernel<T><<<dmc::cdiv(k.M, 256), 256, 0, s>>>(k);
-      return dmc::check_launch("dmc_conv2d");
+    p.family = DMC_CONV_GLDS;
+    if (split) {
+      // (a 2-stage ring with two split blocks per CU and deeper 4 / 5-stage rings measured neutral or slower, round 4)
+      p.splits = gp.splits; p.per = gp.per;
+      p.grid = dim3(dmc::cdiv(k.M, 128), nb128, gp.splits);
+      if (skgn && k.M % 64 == 0 && k.Cout % 8 == 0 && !k.out_f32 && !k.out_nchw && k.Csplit == k.Cout)
+        p.gn = DMC_GN_PART_SPLITK;
+    } else if (gp.splits > 1 || gp.cfg == 2) {
+      p.wm = 1; p.block = 128;   // 64x128 tiles, 2 waves (also where a planned split-K cannot run)
+      p.grid = tiles(64);
+    } else {
+      // 128x128 tiles. Two blocks per CU on a 2-stage ring where there are more tiles than CUs (one round instead of
+      // two; the 8x8 attention qkv GEMM: 384 tiles), and for the big problems (plan_glds cfg 0: the 8-wave 256x128
+      // tile with a 3-stage ring, one block per CU, measured slower: round 2); else the 3-stage ring.
+      if (gp.cfg == 0 || (long)dmc::cdiv(k.M, 128) * nb128 > 256) p.stages = 2;
+      p.grid = tiles(128);
     }
-  }
-  if (sizeof(T) == 2) {
-    const int bn = img_plan(k);
-    if (bn) { launch_img(k, bn, s); return dmc::check_launch("dmc_conv2d"); }
-  }
-  if (sizeof(T) == 2) {
-    const int tpb = gemm1x1_plan(k);
-    if (tpb) {
-      const int NB = k.Cout / 128, ntiles = (k.M / 128) * NB;
-      gemm1x1_persist_kernel<2><<<dmc::cdiv(ntiles, tpb), 256, 0, s>>>(k, ntiles, NB, tpb);
-      return dmc::check_launch("dmc_conv2d");
-    }
-  }
-  if (sizeof(T) == 2 && k.prologue == DMC_PRO_AFFINE_SILU) {
-    int R, nimg;
-    const int hp2 = halo2_pro_plan(k, &R, &nimg);
-    if (hp2) { launch_halo2<true>(k, hp2, R, nimg, s); return dmc::check_launch("dmc_conv2d"); }
-  }
-  if (sizeof(T) == 2 && k.prologue == DMC_PRO_NONE && !dmc::opt(dmc::OPT_NO_GLDS)) {
-    // bf16, plain operands: LDS-DMA pipelined kernel
-    FwdPlan p = plan_glds(k);
-    if (p.splits > 1 && (ws == nullptr || ws_bytes < p.ws || dmc::opt(dmc::OPT_NO_SPLITK))) { p.splits = 1; p.cfg = 2; }
-    if (p.splits > 1) { k.sk = (float*)ws; k.sk_per = p.per; }
-    const bool buf = k.C1 % 64 == 0 && k.C2 % 64 == 0 && k.Kc == k.C1 + k.C2 && k.x1_bytes > 0 &&
-                     (k.C2 == 0 || k.x2_bytes > 0) && k.w_bytes > 0 && !dmc::opt(dmc::OPT_NO_BUFLDS);
-    int R2, nimg2;
-    const int hp2 = (buf && p.splits == 1 && !dmc::opt(dmc::OPT_NO_HALO)) ? halo2_plan(k, &R2, &nimg2) : 0;
-    if (hp2) launch_halo2<false>(k, hp2, R2, nimg2, s);
-    else if (buf) launch_glds<true>(k, p, s);
-    else launch_glds<false>(k, p, s);
-    return dmc::check_launch("dmc_conv2d");
+    return p;
   }
   // register-staged kernel (fp32 parity mode, or a fused prologue)
-  const RegPlan rp = plan_reg(k);
+  p.family = DMC_CONV_REG;
   if (rp.big) {
-    dim3 g(dmc::cdiv(k.M, 128), dmc::cdiv(k.Cout, 128));
-    conv_fwd_kernel<T, 128, 128><<<g, 256, 0, s>>>(k);
-  } else if (rp.splits > 1 && ws != nullptr && ws_bytes >= rp.ws && !dmc::opt(dmc::OPT_NO_SPLITK)) {
+    p.tile = 128;
+    p.grid = dim3(dmc::cdiv(k.M, 128), nb128);
+  } else if (rp.splits > 1 && ws_avail >= rp.ws && !no_splitk) {
     // few 64x64 tiles and a long K (the time-embedding GEMMs, K up to 4992): split K over grid.z
-    k.sk = (float*)ws;
-    k.sk_per = rp.per;
-    dim3 g(dmc::cdiv(k.M, 64), dmc::cdiv(k.Cout, 64), rp.splits);
-    conv_fwd_kernel<T, 64, 64><<<g, 256, 0, s>>>(k);
-    const int Cpad = dmc::cdiv(k.Cout, 64) * 64;
-    const long total = (long)k.M * Cpad / 4;
-    const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    launch_splitk_epilogue<T>(k, rp.splits, Cpad, blocks, s);
+    p.splits = rp.splits; p.per = rp.per;
+    p.grid = dim3(dmc::cdiv(k.M, 64), dmc::cdiv(k.Cout, 64), rp.splits);
   } else {
-    dim3 g(dmc::cdiv(k.M, 64), dmc::cdiv(k.Cout, 64));
-    conv_fwd_kernel<T, 64, 64><<<g, 256, 0, s>>>(k);
+    p.grid = dim3(dmc::cdiv(k.M, 64), dmc::cdiv(k.Cout, 64));
   }
-  return dmc::check_launch("dmc_conv2d");
+  return p;
 }
 
+// Runs a plan: builds nothing but the launches. k carries what the plan decided (gst / gsk / sk set by the caller).
+int launch_conv(const ConvK& k, const ConvPlan& p, float* part, hipStream_t s) {
+  const dim3 g = p.grid;
+  switch (p.family) {
+    case DMC_CONV_NIN_HALO:
+      // reg_epi_ok: the predicate of k.gst and DMC_REG_EPI that the halo kernels evaluate on the device
+      if (reg_epi_ok(k)) conv3x3_nin_kernel<true><<<g, 256, 0, s>>>(k, p.R, p.nimg);
+      else conv3x3_nin_kernel<false><<<g, 256, 0, s>>>(k, p.R, p.nimg);
+      break;
+    case DMC_CONV_NOUT_HALO:
+      if (p.hp == 6) { if (p.npl == 1) conv3x3_nout_kernel<6, 1><<<g, 256, 0, s>>>(k, p.R, p.nimg); else conv3x3_nout_kernel<6, 2><<<g, 256, 0, s>>>(k, p.R, p.nimg); }
+      else if (p.hp == 7) { if (p.npl == 1) conv3x3_nout_kernel<7, 1><<<g, 256, 0, s>>>(k, p.R, p.nimg); else conv3x3_nout_kernel<7, 2><<<g, 256, 0, s>>>(k, p.R, p.nimg); }
+      else { if (p.npl == 1) conv3x3_nout_kernel<9, 1><<<g, 256, 0, s>>>(k, p.R, p.nimg); else conv3x3_nout_kernel<9, 2><<<g, 256, 0, s>>>(k, p.R, p.nimg); }
+      break;
+    case DMC_CONV_NARROW_IN:
+      if (k.dtype_bytes == 4) conv_narrow_in_kernel<float><<<g, 256, 0, s>>>(k);
+      else conv_narrow_in_kernel<bf16_t><<<g, 256, 0, s>>>(k);
+      break;
+    case DMC_CONV_NARROW_OUT:
+      if (k.dtype_bytes == 4) conv_narrow_out_kernel<float><<<g, 256, 0, s>>>(k);
+      else conv_narrow_out_kernel<bf16_t><<<g, 256, 0, s>>>(k);
+      break;
+    case DMC_CONV_IMG:
+      if (k.prologue == DMC_PRO_GN_SILU) {
+        if (k.OH == 8) conv3x3_img_kernel<32, 64, 2, true><<<g, 256, 0, s>>>(k);
+        else conv3x3_img_kernel<16, 32, 4, true><<<g, 256, 0, s>>>(k);
+      } else if (k.OH == 8) {
+        if (p.bn == 16) conv3x3_img_kernel<16, 64, 3><<<g, 256, 0, s>>>(k);
+        else conv3x3_img_kernel<32, 64, 2><<<g, 256, 0, s>>>(k);
+      } else {
+        if (p.bn == 16) conv3x3_img_kernel<16, 32, 4><<<g, 256, 0, s>>>(k);
+        else conv3x3_img_kernel<32, 32, 3><<<g, 256, 0, s>>>(k);
+      }
+      break;
+    case DMC_CONV_GEMM1X1: {
+      const int NB = k.Cout / 128, ntiles = (k.M / 128) * NB;
+      gemm1x1_persist_kernel<2><<<g, 256, 0, s>>>(k, ntiles, NB, p.tpb);
+      break;
+    }
+    case DMC_CONV_HALO:
+      if (p.fused_pro) {
+        if (p.hp == 6) conv3x3_halo2_kernel<6, 3, true><<<g, 256, 0, s>>>(k, p.R, p.nimg);
+        else if (p.hp == 7) conv3x3_halo2_kernel<7, 3, true><<<g, 256, 0, s>>>(k, p.R, p.nimg);
+        else conv3x3_halo2_kernel<9, 2, true><<<g, 256, 0, s>>>(k, p.R, p.nimg);
+      } else {
+        if (p.hp == 6) conv3x3_halo2_kernel<6, 3, false><<<g, 256, 0, s>>>(k, p.R, p.nimg);
+        else if (p.hp == 7) conv3x3_halo2_kernel<7, 3, false><<<g, 256, 0, s>>>(k, p.R, p.nimg);
+        else conv3x3_halo2_kernel<9, 2, false><<<g, 256, 0, s>>>(k, p.R, p.nimg);
+      }
+      break;
+    case DMC_CONV_GLDS:
+      if (p.wm == 1) {
+        if (p.buf) conv_fwd_glds_kernel<1, 2, true><<<g, 128, 0, s>>>(k);
+        else conv_fwd_glds_kernel<1, 2, false><<<g, 128, 0, s>>>(k);
+      } else if (p.stages == 2) {
+        if (p.buf) conv_fwd_glds_kernel<2, 2, true, 2><<<g, 256, 0, s>>>(k);
+        else conv_fwd_glds_kernel<2, 2, false, 2><<<g, 256, 0, s>>>(k);
+      } else {
+        if (p.buf) conv_fwd_glds_kernel<2, 2, true><<<g, 256, 0, s>>>(k);
+        else conv_fwd_glds_kernel<2, 2, false><<<g, 256, 0, s>>>(k);
+      }
+      break;
+    case DMC_CONV_REG:
+      if (k.dtype_bytes == 4) {
+        if (p.tile == 128) conv_fwd_kernel<float, 128, 128><<<g, 256, 0, s>>>(k);
+        else conv_fwd_kernel<float, 64, 64><<<g, 256, 0, s>>>(k);
+      } else {
+        if (p.tile == 128) conv_fwd_kernel<bf16_t, 128, 128><<<g, 256, 0, s>>>(k);
+        else conv_fwd_kernel<bf16_t, 64, 64><<<g, 256, 0, s>>>(k);
+      }
+      break;
+    default: return 0;
+  }
+  if (p.splits > 1) {   // reduce the slab and run the epilogue (with the GroupNorm partials where planned)
+    const int bn = p.family == DMC_CONV_GLDS ? 128 : 64, Cpad = dmc::cdiv(k.Cout, bn) * bn;
+    const long total = (long)k.M * Cpad / 4;
+    const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+    if (p.gn == DMC_GN_PART_SPLITK) launch_splitk_epi_gn(k, p.splits, Cpad, s);
+    else if (k.dtype_bytes == 4) launch_splitk_epilogue<float>(k, p.splits, Cpad, blocks, s);
+    else launch_splitk_epilogue<bf16_t>(k, p.splits, Cpad, blocks, s);
+  }
+  const int rc = dmc::check_launch("dmc_conv2d");
+  if (rc || p.gn != DMC_GN_PART_PASS) return rc;
+  // the chosen kernel's epilogue does not emit them: one pass over the stored output
+  const int nseg = k.M / 64, nch = k.Cout / 8;
+  const int blocks = (int)(((long)nseg * nch + 3) / 4);
+  if (k.out_f32 || k.dtype_bytes == 4) gn_part_kernel<float><<<blocks, 256, 0, s>>>(k.y1, k.ldy1, nseg, nch, part);
+  else gn_part_kernel<bf16_t><<<blocks, 256, 0, s>>>(k.y1, k.ldy1, nseg, nch, part);
+  return dmc::check_launch("dmc_conv2d (GroupNorm partials)");
+}
+
+// Descriptor -> (ConvK, plan) for dmc_conv2d and dmc_conv2d_plan: the checks both make before anything runs.
+int plan_desc(const dmc_conv_desc* d, size_t ws_avail, ConvK& k, ConvPlan& p) {
+  if (k.M != 0 && k.Cout != 0 && d->gn_part)
+    DMC_REQUIRE(k.OHW % 64 == 0 && k.Cout % 8 == 0 && k.Csplit == k.Cout && !k.out_nchw && k.ldy1 % 4 == 0,
+                "conv: GroupNorm partials need OH*OW %% 64 == 0, Cout %% 8 == 0 and one NHWC output");
+  p = plan_conv(k, d->gn_part != nullptr, ws_avail);
+  DMC_REQUIRE(p.family == DMC_CONV_NONE || k.prologue != DMC_PRO_GN_SILU || p.fused_pro,
+              "conv: DMC_PRO_GN_SILU is taken only by the small-map conv (dmc_conv_halo_prologue says when)");
+  return 0;
+}
 
 }  // namespace
 
 extern "C" size_t dmc_conv2d_workspace(const dmc_conv_desc* d) {
   ConvK k;
   if (fill_convk(d, nullptr, nullptr, nullptr, nullptr, nullptr, k)) return 0;
-  if (k.M == 0) return 0;
-  if (d->dtype != DMC_BF16 || d->prologue != DMC_PRO_NONE || dmc::opt(dmc::OPT_NO_GLDS)) return plan_reg(k).ws;
-  return plan_glds(k).ws;
+  return plan_conv(k, false, 0).ws_report;
 }
 
 extern "C" int dmc_conv2d_fused_epilogue(const dmc_conv_desc* d, size_t ws_bytes) {
   ConvK k;
-  if (fill_convk(d, nullptr, nullptr, nullptr, nullptr, nullptr, k) || k.M == 0 || k.Cout == 0) return 0;
-  // the planners only ask whether a workspace of ws_bytes is present
-  const void* ws = ws_bytes ? (const void*)d : nullptr;
-  int f = 0;
-  if (k.OHW % 64 == 0 && k.Cout % 8 == 0 && epi_stats_ok(k, ws, ws_bytes)) f |= DMC_FUSED_GN_STATS;
-  return f;
+  if (fill_convk(d, nullptr, nullptr, nullptr, nullptr, nullptr, k)) return 0;
+  return plan_conv(k, true, ws_bytes).gn == DMC_GN_PART_KERNEL ? DMC_FUSED_GN_STATS : 0;
+}
+
+extern "C" int dmc_conv_halo_prologue(const dmc_conv_desc* d) {
+  ConvK k;
+  if (d == nullptr || fill_convk(d, nullptr, nullptr, nullptr, nullptr, nullptr, k)) return 0;
+  return plan_conv(k, false, 0).fused_pro ? 1 : 0;
+}
+
+extern "C" int dmc_conv2d_plan(const dmc_conv_desc* d, size_t ws_bytes, dmc_conv_plan* out) {
+  ConvK k;
+  ConvPlan p;
+  // the plan of a launch that passes y2 where the descriptor splits its output (nothing is launched or written
+  // here; dmc_conv2d keeps such a conv off the persistent GEMM when its y2 is NULL)
+  static char y2_present;
+  if (fill_convk(d, nullptr, nullptr, nullptr, nullptr, &y2_present, k) || plan_desc(d, ws_bytes, k, p)) return 1;
+  out->family = p.family;
+  out->grid[0] = p.grid.x; out->grid[1] = p.grid.y; out->grid[2] = p.grid.z;
+  out->block = p.block;
+  out->splits = p.splits;
+  out->gn_part = p.gn;
+  out->fused_prologue = p.fused_pro;
+  out->ws_bytes = p.ws_report;
+  return 0;
 }
 
 extern "C" int dmc_conv2d(const dmc_conv_desc* d, const void* x1, const void* x2, const void* w, void* y1,
                           void* y2, void* workspace, size_t ws_bytes, void* stream) {
   ConvK k;
-  if (fill_convk(d, x1, x2, w, y1, y2, k)) return 1;
-  hipStream_t s = dmc::as_stream(stream);
-  if (k.M == 0 || k.Cout == 0) return 0;
-  float* const part = d->gn_part;
-  if (part) {
-    DMC_REQUIRE(k.OHW % 64 == 0 && k.Cout % 8 == 0 && k.Csplit == k.Cout && !k.out_nchw && k.ldy1 % 4 == 0,
-                "conv: GroupNorm partials need OH*OW %% 64 == 0, Cout %% 8 == 0 and one NHWC output");
-    k.gst = epi_stats_ok(k, workspace, ws_bytes) ? part : nullptr;
-  }
-  // split-K launches: the split-K epilogue emits the partials in its pass (DMC_NO_SKGN=1: a separate pass)
-  int gsk_done = 0;
-  if (part && !k.gst && !dmc::opt(dmc::OPT_NO_SKGN)) { k.gsk = part; k.gsk_done = &gsk_done; }
-  const int rc = d->dtype == DMC_F32 ? launch_fwd<float>(k, workspace, ws_bytes, s)
-                                     : launch_fwd<bf16_t>(k, workspace, ws_bytes, s);
-  if (rc) return rc;
-  if (!part || k.gst || gsk_done) return 0;
-  // the chosen kernel's epilogue does not emit them: one pass over the stored output
-  const int nseg = k.M / 64, nch = k.Cout / 8;
-  const int blocks = (int)(((long)nseg * nch + 3) / 4);
-  if (k.out_f32 || d->dtype == DMC_F32)
-    gn_part_kernel<float><<<blocks, 256, 0, s>>>(k.y1, k.ldy1, nseg, nch, part);
-  else
-    gn_part_kernel<bf16_t><<<blocks, 256, 0, s>>>(k.y1, k.ldy1, nseg, nch, part);
-  return dmc::check_launch("dmc_conv2d (GroupNorm partials)");
+  ConvPlan p;
+  if (fill_convk(d, x1, x2, w, y1, y2, k) || plan_desc(d, workspace ? ws_bytes : 0, k, p)) return 1;
+  if (p.gn == DMC_GN_PART_KERNEL) k.gst = d->gn_part;
+  if (p.gn == DMC_GN_PART_SPLITK) k.gsk = d->gn_part;
+  if (p.splits > 1) { k.sk = (float*)workspace; k.sk_per = p.per; }
+  return launch_conv(k, p, d->gn_part, dmc::as_stream(stream));
 }
+
 
 extern "C" int dmc_pack_weight(int pack_mode, int dtype, const float* w, int Cout, int Cin, int kh, int kw, int Kc,
                                void* dst, void* stream) {
@@ -2536,17 +2598,6 @@ extern "C" int dmc_pack_weight(int pack_mode, int dtype, const float* w, int Cou
   else
     pack_weight_kernel<bf16_t><<<blocks, 256, 0, s>>>(pack_mode, w, Cout, Cin, kh, kw, Kc, (bf16_t*)dst);
   return dmc::check_launch("dmc_pack_weight");
-}
-
-// 1 when dmc_conv2d runs this descriptor on the halo kernel with its GN-affine+SiLU prologue applied to the
-// resident halo (bf16 3x3 stride-1, no dropout): the caller can skip materialising the GroupNorm output.
-extern "C" int dmc_conv_halo_prologue(const dmc_conv_desc* d) {
-  if (d == nullptr || d->dtype != DMC_BF16) return 0;
-  ConvK k;
-  if (fill_convk(d, nullptr, nullptr, nullptr, nullptr, nullptr, k) != 0) return 0;
-  if (k.prologue == DMC_PRO_GN_SILU) return img_plan(k) ? 1 : 0;
-  int R, nimg;
-  return halo2_pro_plan(k, &R, &nimg) ? 1 : 0;
 }
 
 extern "C" int dmc_pack_tiles(const dmc_pack_job* j, int job_index, int* tiles, int cap) {

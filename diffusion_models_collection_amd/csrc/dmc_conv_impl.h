@@ -21,7 +21,6 @@ struct ConvK {
   float* gst;  // GroupNorm partials from the epilogue: [M/64][Cout/8] x (mean, M2) (nullptr: off)
   float* wgb;  // wgrad: per-split bias partials [split][Cpad] = sum over the split's pixels of dy (nullptr: off)
   float* gsk;  // split-K launches: GroupNorm partials written by the split-K epilogue (nullptr: off)
-  int* gsk_done;  // host flag: set when the launch path emitted gsk
   int M;      // N*OH*OW output pixels
   int OHW;    // OH*OW
   float* sk;  // split-K partial slab (nullptr: no split)
@@ -127,13 +126,19 @@ DMC_DEV void dma_pieces(const void* base, int nbytes, char* dst, const unsigned*
       __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (LDS_AS void*)(dst + p * 1024), 16, off[p] + add, 0, 0, 0);
 }
 
+// A 3x3 stride-1 conv whose output has the size of its input, with the taps on a +-1 grid walked in either
+// direction (forward, or the flipped taps of an input gradient): what every halo / whole-image kernel assumes.
+bool same_size_3x3(const ConvK& k) {
+  if (k.mode != DMC_MODE_NORMAL || k.stride != 1 || k.ntaps != 9 || k.tkw != 3) return false;
+  if (!((k.tdy0 == -1 && k.tsy == 1) || (k.tdy0 == 1 && k.tsy == -1))) return false;
+  if (!((k.tdx0 == -1 && k.tsx == 1) || (k.tdx0 == 1 && k.tsx == -1))) return false;
+  return k.OH == k.H && k.OW == k.W;
+}
+
 // Geometry of the halo kernel for this conv, or false if it does not apply.
 // Returns the DMA pieces per wave (6 or 7) the halo needs, 0 if the halo kernels do not apply.
 int halo_plan(const ConvK& k, int* R, int* nimg, int maxhp = 7) {
-  if (k.mode != DMC_MODE_NORMAL || k.stride != 1 || k.ntaps != 9 || k.tkw != 3) return 0;
-  if (!((k.tdy0 == -1 && k.tsy == 1) || (k.tdy0 == 1 && k.tsy == -1))) return 0;
-  if (!((k.tdx0 == -1 && k.tsx == 1) || (k.tdx0 == 1 && k.tsx == -1))) return 0;
-  if (k.OH != k.H || k.OW != k.W) return 0;
+  if (!same_size_3x3(k)) return 0;
   const int ohw = k.OH * k.OW;
   if (ohw % 256 == 0 && 256 % k.OW == 0) { *nimg = 1; *R = 256 / k.OW; }
   else if (256 % ohw == 0 && k.N % (256 / ohw) == 0) { *nimg = 256 / ohw; *R = k.OH; }
@@ -145,10 +150,7 @@ int halo_plan(const ConvK& k, int* R, int* nimg, int maxhp = 7) {
 // Geometry of the two-blocks-per-CU halo kernel (128-pixel tiles): halo pieces per wave (6, 7 or 9), 0 if it
 // does not apply.
 int halo2_plan(const ConvK& k, int* R, int* nimg) {
-  if (k.mode != DMC_MODE_NORMAL || k.stride != 1 || k.ntaps != 9 || k.tkw != 3) return 0;
-  if (!((k.tdy0 == -1 && k.tsy == 1) || (k.tdy0 == 1 && k.tsy == -1))) return 0;
-  if (!((k.tdx0 == -1 && k.tsx == 1) || (k.tdx0 == 1 && k.tsx == -1))) return 0;
-  if (k.OH != k.H || k.OW != k.W) return 0;
+  if (!same_size_3x3(k)) return 0;
   const int ohw = k.OH * k.OW;
   if (ohw % 128 == 0 && 128 % k.OW == 0) { *nimg = 1; *R = 128 / k.OW; }
   else if (128 % ohw == 0 && k.N % (128 / ohw) == 0) { *nimg = 128 / ohw; *R = k.OH; }
@@ -210,7 +212,7 @@ int fill_convk(const dmc_conv_desc* d, const void* x1, const void* x2, const voi
   k.act = d->act; k.ypre = (char*)d->y_pre; k.ldpre = d->ld_pre;
   k.gst = nullptr;   // set by dmc_conv2d when the chosen kernel emits the GroupNorm partials
   k.wgb = nullptr;   // set by dmc_conv2d_wgrad when the bias gradient is requested
-  k.gsk = nullptr; k.gsk_done = nullptr;
+  k.gsk = nullptr;   // set by dmc_conv2d when the split-K epilogue emits them
   k.reg_epi = (int)dmc::opt(dmc::OPT_REG_EPI);
   k.M = d->N * d->OH * d->OW; k.OHW = d->OH * d->OW;
   k.sk = nullptr; k.sk_per = 0;

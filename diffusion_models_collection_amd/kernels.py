@@ -148,6 +148,16 @@ def conv_fused(d):
     return LIB.dmc_conv2d_fused_epilogue(ctypes.byref(d), LIB.dmc_conv2d_workspace(ctypes.byref(d)))
 
 
+def conv_plan(d, ws_bytes=None):
+    """include/dmc.h dmc_conv2d_plan: the launch plan (L.ConvPlan) dmc_conv2d follows for `d` with a workspace of
+    ws_bytes (default: what conv() passes). Host only."""
+    if ws_bytes is None:
+        ws_bytes = LIB.dmc_conv2d_workspace(ctypes.byref(d))
+    p = L.ConvPlan()
+    check(LIB.dmc_conv2d_plan(ctypes.byref(d), ws_bytes, ctypes.byref(p)), "dmc_conv2d_plan")
+    return p
+
+
 def upsample2x(dtype, x, C):
     """Nearest x2 upsample of an NHWC [N, H, W, ld] activation's first C channels -> [N, 2H, 2W, C]."""
     N, H, W, ld = x.shape

@@ -118,6 +118,33 @@ int dmc_conv_halo_prologue(const dmc_conv_desc* d);
  * opposed to one extra pass over the stored output: DMC_FUSED_GN_STATS (gn_part). */
 int dmc_conv2d_fused_epilogue(const dmc_conv_desc* d, size_t ws_bytes);
 enum { DMC_FUSED_GN_STATS = 1 };
+/* The launch plan dmc_conv2d(d, ..., ws_bytes) follows, computed on the host without touching a device (d->gn_part
+ * != NULL is the request for the GroupNorm partials, as in dmc_conv2d). The three queries above report fields of
+ * the same plan. Returns nonzero (dmc_last_error) where dmc_conv2d would reject the descriptor. */
+enum { DMC_CONV_NONE = 0,        /* empty problem: nothing is launched */
+       DMC_CONV_NIN_HALO = 1,    /* halo'd narrow-input 3x3 */
+       DMC_CONV_NOUT_HALO = 2,   /* halo'd narrow-output 3x3 */
+       DMC_CONV_NARROW_IN = 3,   /* generic narrow-input */
+       DMC_CONV_NARROW_OUT = 4,  /* generic narrow-output */
+       DMC_CONV_IMG = 5,         /* whole-image small-map 3x3 (4x4 / 8x8) */
+       DMC_CONV_GEMM1X1 = 6,     /* persistent 1x1 GEMM */
+       DMC_CONV_HALO = 7,        /* 128-pixel halo 3x3 */
+       DMC_CONV_GLDS = 8,        /* LDS-DMA implicit GEMM */
+       DMC_CONV_REG = 9 };       /* register-staged implicit GEMM */
+enum { DMC_GN_PART_NONE = 0,     /* not requested */
+       DMC_GN_PART_KERNEL = 1,   /* the conv kernel's epilogue (DMC_FUSED_GN_STATS) */
+       DMC_GN_PART_SPLITK = 2,   /* the split-K reduction's epilogue */
+       DMC_GN_PART_PASS = 3 };   /* a separate pass over the stored output */
+typedef struct dmc_conv_plan {
+  int family;                /* DMC_CONV_* */
+  unsigned grid[3];          /* grid (blocks) and block size (threads) of the main launch */
+  int block;
+  int splits;                /* split-K factor (1: none; > 1: a reduction launch follows) */
+  int gn_part;               /* DMC_GN_PART_* */
+  int fused_prologue;        /* what dmc_conv_halo_prologue answers */
+  size_t ws_bytes;           /* what dmc_conv2d_workspace answers */
+} dmc_conv_plan;
+int dmc_conv2d_plan(const dmc_conv_desc* d, size_t ws_bytes, dmc_conv_plan* out);
 int dmc_conv2d(const dmc_conv_desc* d, const void* x1, const void* x2, const void* w,
                void* y1, void* y2, void* workspace, size_t ws_bytes, void* stream);
 
