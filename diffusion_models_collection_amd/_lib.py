@@ -64,6 +64,15 @@ class WgradJob(ctypes.Structure):
                 ("scale", ctypes.c_float), ("layout", ctypes.c_int)]
 
 
+class WgradPlan(ctypes.Structure):
+    """include/dmc.h dmc_wgrad_plan"""
+    _fields_ = [("kind", _c_int), ("grid", ctypes.c_uint * 3), ("block", _c_int), ("splits", _c_int),
+                ("layout", _c_int), ("group_kind", _c_int), ("ws_bytes", _c_size)]
+
+
+WGRAD_KINDS = ("", "img4", "pipe", "halo", "gemm1x1", "generic")   # include/dmc.h DMC_WGRAD_* (by code)
+
+
 class WgradGroupItem(ctypes.Structure):
     """include/dmc.h dmc_wgrad_group_item"""
     _fields_ = [("d", ctypes.POINTER(ConvDesc)), ("dy", ctypes.c_void_p), ("ld_dy", ctypes.c_int),
@@ -112,6 +121,7 @@ def _load():
         "dmc_conv2d_wgrad_partial": (_c_int, [ctypes.POINTER(ConvDesc), _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_f,
                                               ctypes.POINTER(WgradJob), _c_p]),
         "dmc_wgrad_reduce_batch": (_c_int, [ctypes.POINTER(WgradJob), _c_int, _c_p]),
+        "dmc_conv2d_wgrad_plan": (_c_int, [ctypes.POINTER(ConvDesc), _c_int, ctypes.POINTER(WgradPlan)]),
         "dmc_conv2d_wgrad_group_ok": (_c_int, [ctypes.POINTER(ConvDesc), _c_int]),
         "dmc_conv2d_wgrad_group_workspace": (_c_size, [ctypes.POINTER(WgradGroupItem), _c_int,
                                                        ctypes.POINTER(_c_size)]),

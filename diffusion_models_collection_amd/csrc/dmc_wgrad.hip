@@ -2,12 +2,14 @@
 // orientation): dW[co][c][t] = sum over pixels of dy[pix][co] * x[coord(pix, t)][c] (models/unet.py:34-60 conv
 // weights, :81-82 qkv / proj, :106 / :116 down / up sampling, :167-172 / :188 / :237-241), as per-split fp32 partial
 // sums and a deterministic split reduction:
+//   * wgrad3x3_img4_kernel: 3x3 stride-1 on 4x4 images, whole 512-pixel chunks (no slab: reduces in the kernel);
 //   * wgrad3x3_pipe_kernel: 3x3 stride-1 on 32/16-wide maps and 8x8 / 4x4 images (dw-shaped slab);
 //   * wgrad3x3_halo2_kernel: the other 3x3 stride-1 halo geometries (64x64);
 //   * wgrad1x1_glds_kernel: 1x1 / Linear (dw-shaped slab);
 //   * conv_wgrad_kernel: everything else ([split][kk][co] slab);
 //   * wgrad_reduce_batch_kernel: the split reductions, up to 32 per launch (dmc_wgrad_reduce_batch).
 // The pipelined 3x3 and the 1x1 kernels take a by-value table of up to 8 jobs (dmc_conv2d_wgrad_group).
+// The kernels come first; the host half at the end of the file picks one per call (plan_wgrad, in the order above).
 #include <algorithm>
 #include <atomic>
 
@@ -1026,58 +1028,6 @@ __global__ __launch_bounds__(1024) void wgrad_reduce_batch_kernel(WgBatch b) {
 }
 
 
-int wgrad_splits(const dmc_conv_desc* d, int* pps) {
-  const int sp = d->dtype == DMC_F32 ? 16 : 32;   // conv_wgrad_kernel's pixels per stage (SP)
-  const long M = (long)d->N * d->OH * d->OW;
-  const long KK = (long)d->ntaps * d->Kc;
-  const long tiles = (long)dmc::cdiv(KK, 128) * dmc::cdiv(d->Cout, 128);
-  const long target = dmc::opt(dmc::OPT_WG_BLOCKS);   // A/B knob
-  long splits = (target + tiles - 1) / tiles;
-  // at least DMC_WG_MINPIX pixels per split (>= 4 stages): the fp32 slab is splits x KK x Cout, written and read back
-  const long minpix = dmc::opt(dmc::OPT_WG_MINPIX) > 4 * sp ? dmc::opt(dmc::OPT_WG_MINPIX) : 4 * sp;
-  const long max_splits = (M + minpix - 1) / minpix;
-  if (splits > max_splits) splits = max_splits;
-  // (a cap on the slab against the operand bytes measured slower at every ratio, round 4: no cap 9069 img/s,
-  // 8x 9011, 4x 8749, 2x 8164 -- the blocks a cap removes cost more than the slab bytes it saves)
-  if (splits < 1) splits = 1;
-  long per = (M + splits - 1) / splits;
-  per = (per + sp - 1) / sp * sp;
-  splits = (M + per - 1) / per;
-  *pps = (int)per;
-  return (int)splits;
-}
-
-// Halo weight-gradient plan: applies to bf16 3x3 stride-1 convs the halo forward kernel handles, with
-// 64-aligned channel sources. Splits the 256-pixel tiles so that ~256 blocks run (one per CU).
-struct WgHaloPlan {
-  bool ok;
-  int R, nimg, splits, tps, hp;
-};
-
-WgHaloPlan wgrad_halo_plan(const dmc_conv_desc* d) {
-  WgHaloPlan p{false, 0, 0, 1, 0, 0};
-  if (d->dtype != DMC_BF16 || dmc::opt(dmc::OPT_NO_HALO)) return p;
-  ConvK k;
-  if (fill_convk(d, nullptr, nullptr, nullptr, nullptr, nullptr, k)) return p;
-  if (k.C1 % 64 || k.C2 % 64 || k.Kc != k.C1 + k.C2 || k.x1_bytes == 0 || (k.C2 && k.x2_bytes == 0)) return p;
-  p.hp = halo_plan(k, &p.R, &p.nimg, 7);
-  if (!p.hp) return p;
-  const int ntiles = k.M / 256;
-  const int base = (k.Kc / 64) * dmc::cdiv(k.Cout, 128);
-  const int target = (int)dmc::opt(dmc::OPT_WG_HALO_TARGET);   // blocks of 128 co (the 64-co kernel runs twice as many)
-  int sp = (target + base - 1) / base;
-  if (sp > ntiles) sp = ntiles;
-  if (sp < 1) sp = 1;
-  p.tps = (ntiles + sp - 1) / sp;
-  p.splits = (ntiles + p.tps - 1) / p.tps;
-  p.ok = true;
-  return p;
-}
-
-// Pipelined weight-gradient plan (wgrad3x3_pipe_kernel): bf16 3x3 stride-1 convs on halo2_plan's 128-pixel geometry
-// with 32- or 16-wide maps (rows of one image) or 8x8 maps (two images per tile), 64-aligned channel sources, no
-// prologue, ld_dy % 8 == 0. Returns OW (the template argument) or 0; splits the tiles so that ~DMC_WG_HALO_TARGET x 2
-// blocks of 64 x 64 run.
 // ---------------------------------------------------------------------------------------------
 // Whole-image weight gradient of the 4x4 levels (round 6; models/unet.py:34-60 at the deepest resolution). At B = 128
 // a 4x4 256 -> 256 layer reduces over only M = 2048 pixels, so one block can take ALL of them for its output tile and
@@ -1280,191 +1230,350 @@ __global__ __launch_bounds__(256) void wgrad3x3_img4_kernel(ConvK a, const char*
   }
 }
 
-// The whole-image 4x4 weight gradient applies (bf16 3x3 stride 1, forward taps, 4x4 maps, whole 512-pixel chunks,
-// 16-aligned channels, DMC_WG_IMG4 = 1).
-bool wgrad_img4_ok(const dmc_conv_desc* d, const ConvK& k, int ld_dy) {
-  if (d->dtype != DMC_BF16 || !dmc::opt(dmc::OPT_WG_IMG4) || k.prologue != DMC_PRO_NONE) return false;
-  if (k.mode != DMC_MODE_NORMAL || k.stride != 1 || k.ntaps != 9 || k.tkw != 3 || k.OH != 4 || k.OW != 4 || k.H != 4 ||
-      k.W != 4)
-    return false;
-  if (k.tdy0 != -1 || k.tsy != 1 || k.tdx0 != -1 || k.tsx != 1) return false;
+// ---------------------------------------------------------------------------------------------
+// Host half. plan_wgrad decides once per (descriptor, ld_dy) which kernel runs and how its work is split;
+// launch_wgrad runs a plan; the grouped entry builds its plan from the jobs' own plans (wg_group_plan); the queries
+// report fields of the same plans. DESIGN.md "Weight-gradient dispatch" has the order, each kind's requirements and
+// the quirks that are kept as they were.
+
+// conv_wgrad_kernel's split: ~DMC_WG_BLOCKS blocks, whole stages, at least DMC_WG_MINPIX pixels per split. Also the
+// bound of the 1x1 kind's split count (wg1x1_pps) and a term of the workspace query.
+int wgrad_splits(const dmc_conv_desc* d, int* pps) {
+  const int sp = d->dtype == DMC_F32 ? 16 : 32;   // conv_wgrad_kernel's pixels per stage (SP)
+  const long M = (long)d->N * d->OH * d->OW;
+  const long KK = (long)d->ntaps * d->Kc;
+  const long tiles = (long)dmc::cdiv(KK, 128) * dmc::cdiv(d->Cout, 128);
+  const long target = dmc::opt(dmc::OPT_WG_BLOCKS);   // A/B knob
+  long splits = (target + tiles - 1) / tiles;
+  // at least DMC_WG_MINPIX pixels per split (>= 4 stages): the fp32 slab is splits x KK x Cout, written and read back
+  const long minpix = dmc::opt(dmc::OPT_WG_MINPIX) > 4 * sp ? dmc::opt(dmc::OPT_WG_MINPIX) : 4 * sp;
+  const long max_splits = (M + minpix - 1) / minpix;
+  if (splits > max_splits) splits = max_splits;
+  // (a cap on the slab against the operand bytes measured slower at every ratio, round 4: no cap 9069 img/s,
+  // 8x 9011, 4x 8749, 2x 8164 -- the blocks a cap removes cost more than the slab bytes it saves)
+  if (splits < 1) splits = 1;
+  long per = (M + splits - 1) / splits;
+  per = (per + sp - 1) / sp * sp;
+  splits = (M + per - 1) / per;
+  *pps = (int)per;
+  return (int)splits;
+}
+
+struct WgPlan {
+  bool ok;             // false: fill_convk or the ld_dy alignment rejected the call (dmc_last_error says why)
+  int kind;            // DMC_WGRAD_*
+  int ow;              // PIPE: the map width, wgrad3x3_pipe_kernel's template argument
+  int hp, R, nimg;     // HALO: DMA pieces per wave (the template argument), rows and images of a 256-pixel tile
+  int splits;          // 0 (IMG4): the kernel finishes dw itself, no slab and no reduction
+  int per;             // one split's work: tiles (PIPE: 128 pixels, 64 at width 4; HALO: 256 pixels) or pixels
+                       // (GEMM1X1, GENERIC)
+  int units;           // PIPE / GEMM1X1: the job's work in the units of `per`
+  long base;           // PIPE / GEMM1X1: output tiles = blocks per split
+  dim3 grid;           // the main launch of a single-layer call
+  int block;
+  int layout, Cpad;    // dmc_wgrad_job's: the slab layout and the reduce pitch
+  size_t slab_floats;  // the weight partials of all splits
+  size_t bias_off;     // floats from the workspace to the bias partials [splits][Cpad]
+  int ld_dy;
+  ConvK k;             // without pointers: the launcher binds them
+};
+
+bool wg_forward_taps(const ConvK& k) { return k.tdy0 == -1 && k.tsy == 1 && k.tdx0 == -1 && k.tsx == 1; }
+// dy through a buffer resource: 32-bit offsets
+bool wg_dy_fits(const ConvK& k, int ld_dy) { return (size_t)k.M * ld_dy * 2 < 0x7fff0000u; }
+// what the pipelined and the halo kinds share: bf16 sources DMA'd as whole 64-channel planes that fill Kc
+bool wg_dma_sources_ok(const ConvK& k) {
+  return k.dtype_bytes == 2 && k.C1 % 64 == 0 && k.C2 % 64 == 0 && k.Kc == k.C1 + k.C2 && k.x1_bytes != 0 &&
+         (k.C2 == 0 || k.x2_bytes != 0);
+}
+
+// The whole-image 4x4 kind applies (bf16 3x3 stride 1, forward taps, 4x4 maps, whole 512-pixel chunks, 16-aligned
+// channels, DMC_WG_IMG4 = 1).
+bool wg_img4_ok(const ConvK& k, int ld_dy) {
+  if (k.dtype_bytes != 2 || !dmc::opt(dmc::OPT_WG_IMG4) || k.prologue != DMC_PRO_NONE) return false;
+  if (!same_size_3x3(k) || !wg_forward_taps(k) || k.OH != 4 || k.OW != 4) return false;
   if (k.M % kWiPch || k.M / kWiPch < 1 || k.C1 % 16 || k.C2 % 16 || k.Cout % 16 || ld_dy % 8 || k.ld1 % 8 ||
       (k.C2 && k.ld2 % 8) || k.x1_bytes == 0 || (k.C2 && k.x2_bytes == 0))
     return false;
-  return (size_t)k.M * ld_dy * 2 < 0x7fff0000u;
+  return wg_dy_fits(k, ld_dy);
 }
 
-struct WgPipePlan {
-  int ow, splits, tps;
-};
-WgPipePlan wgrad_pipe_plan(const dmc_conv_desc* d, int ld_dy) {
-  WgPipePlan p{0, 1, 0};
-  if (d->dtype != DMC_BF16 || dmc::opt(dmc::OPT_NO_HALO) || dmc::opt(dmc::OPT_WG_PIPE) == 0) return p;
-  ConvK k;
-  if (fill_convk(d, nullptr, nullptr, nullptr, nullptr, nullptr, k)) return p;
-  if (k.C1 % 64 || k.C2 % 64 || k.Kc != k.C1 + k.C2 || k.x1_bytes == 0 || (k.C2 && k.x2_bytes == 0)) return p;
+// The pipelined kind (wgrad3x3_pipe_kernel) applies: forward same-size 3x3 on 32- or 16-wide maps (rows of one image,
+// whole 128-pixel tiles per image), 8x8 maps (two images per tile) or 4x4 maps (four images per 64-pixel tile), no
+// prologue, ld_dy % 8 == 0. Fills ow, units, base and the split: ~DMC_WG_HALO_TARGET blocks of two 64 x 64 halves.
+bool wg_pipe_fits(const ConvK& k, int ld_dy, WgPlan& p) {
+  if (dmc::opt(dmc::OPT_NO_HALO) || dmc::opt(dmc::OPT_WG_PIPE) == 0 || !wg_dma_sources_ok(k)) return false;
   // any Cout with an 8-aligned dy pitch: the dy DMA reads whole 16-byte chunks, so the pitch padding of a narrow dy
   // (the output conv's 3 channels in a pitch of 8) lands in accumulator rows co >= Cout, which are never stored
-  if (k.prologue != DMC_PRO_NONE || ld_dy % 8) return p;
-  if ((size_t)k.M * ld_dy * 2 >= 0x7fff0000u) return p;
-  if (k.mode != DMC_MODE_NORMAL || k.stride != 1 || k.ntaps != 9 || k.tkw != 3 || k.OH != k.H || k.OW != k.W) return p;
-  if (k.tdy0 != -1 || k.tsy != 1 || k.tdx0 != -1 || k.tsx != 1) return p;   // the forward taps (weight gradient)
-  // WgPipeGeo: rows of one image (32 / 16 wide, whole 128-pixel tiles per image), two 8x8 or four 4x4 images per tile
-  const bool ok = ((k.OW == 32 || k.OW == 16) && k.OH % (128 / k.OW) == 0) || (k.OW == 8 && k.OH == 8 && k.N % 2 == 0) ||
-                  (k.OW == 4 && k.OH == 4 && k.N % 4 == 0);
-  if (!ok) return p;
-  const int ntiles = k.M / (k.OW == 4 ? 64 : 128);
-  const long base = (long)(k.Kc / 64) * dmc::cdiv(k.Cout, 64);
-  // 512-thread blocks (two 64 x 64 halves): one per CU, never more than one round of them (264 blocks for 256 CUs
-  // measured 1.4x slower than 192)
-  // 4x4 maps: half the blocks (each half-block two 64-pixel tiles instead of one; half the slab): 28.5 vs 31.1 us
-  // per 256 -> 256 layer (scripts/wgrad_probe2.py, round 5)
-  const long target = dmc::opt(dmc::OPT_WG_HALO_TARGET) / (k.OW == 4 ? 2 : 1);
-  long sp = target / base;
-  if (sp > ntiles) sp = ntiles;
-  if (sp < 1) sp = 1;
-  p.tps = (int)((ntiles + sp - 1) / sp);
-  p.splits = (ntiles + p.tps - 1) / p.tps;
+  if (k.prologue != DMC_PRO_NONE || ld_dy % 8 || !wg_dy_fits(k, ld_dy)) return false;
+  if (!same_size_3x3(k) || !wg_forward_taps(k)) return false;
+  const bool geo = ((k.OW == 32 || k.OW == 16) && k.OH % (128 / k.OW) == 0) || (k.OW == 8 && k.OH == 8 && k.N % 2 == 0) ||
+                   (k.OW == 4 && k.OH == 4 && k.N % 4 == 0);
+  if (!geo) return false;
   p.ow = k.OW;
-  return p;
+  p.units = k.M / (k.OW == 4 ? 64 : 128);
+  p.base = (long)(k.Kc / 64) * dmc::cdiv(k.Cout, 64);
+  // 512-thread blocks: one per CU, never more than one round of them (264 blocks for 256 CUs measured 1.4x slower
+  // than 192). 4x4 maps: half the blocks (each half-block two 64-pixel tiles instead of one; half the slab): 28.5 vs
+  // 31.1 us per 256 -> 256 layer (scripts/wgrad_probe2.py, round 5)
+  const long target = dmc::opt(dmc::OPT_WG_HALO_TARGET) / (k.OW == 4 ? 2 : 1);
+  const long sp = std::max(1L, std::min(target / p.base, (long)p.units));
+  p.per = (int)((p.units + sp - 1) / sp);
+  return true;
 }
 
-WgPipeJob wg_pipe_job(const ConvK& k, const dmc_conv_desc* d, const void* dy, int ld_dy, float* slab, float* wgb) {
-  WgPipeJob j;
-  j.x1 = k.x1; j.x2 = k.x2; j.dy = (const char*)dy;
-  j.slab = slab; j.wgb = wgb;
-  j.x1_bytes = k.x1_bytes; j.x2_bytes = k.x2_bytes; j.dy_bytes = (int)((size_t)k.M * ld_dy * 2);
-  j.ld1 = k.ld1; j.ld2 = k.ld2; j.ld_dy = ld_dy;
-  j.C1 = k.C1; j.C2 = k.C2; j.Cout = k.Cout; j.H = k.H; j.OHW = k.OHW;
-  j.ntiles = k.M / (k.OW == 4 ? 64 : 128);
-  j.ncb = d->Kc / 64; j.nob = dmc::cdiv(d->Cout, 64);
-  j.Cpad = dmc::cdiv(d->Cout, 128) * 128;
-  return j;
+// The round-4 halo kind (wgrad3x3_halo2_kernel) applies: a same-size 3x3 on halo_plan's 256-pixel geometry at 6 or 7
+// pieces per wave (64x64 maps; the smaller maps when the pipelined kind is off). Fills hp, R, nimg and the split: the
+// 256-pixel tiles cut so that ~DMC_WG_HALO_TARGET blocks of 128 co would run (the 64-co kernel runs twice as many).
+bool wg_halo_fits(const ConvK& k, WgPlan& p) {
+  if (dmc::opt(dmc::OPT_NO_HALO) || !wg_dma_sources_ok(k)) return false;
+  int R, nimg;
+  const int hp = halo_plan(k, &R, &nimg, 7);
+  if (!hp) return false;
+  p.hp = hp; p.R = R; p.nimg = nimg;
+  const int ntiles = k.M / 256;
+  const int base = (k.Kc / 64) * dmc::cdiv(k.Cout, 128);
+  const int target = (int)dmc::opt(dmc::OPT_WG_HALO_TARGET);
+  const int sp = std::max(1, std::min((target + base - 1) / base, ntiles));
+  p.per = (ntiles + sp - 1) / sp;
+  p.splits = (ntiles + p.per - 1) / p.per;
+  return true;
 }
 
-// wgrad1x1_glds_kernel applies: 1x1 stride-1 bf16 (Linear-shaped), whole 64-pixel stages, 8-aligned channels and
-// pitches, a second source only behind a 128-aligned first one, 32-bit buffer offsets
-bool wg1x1_ok(const dmc_conv_desc* d, const ConvK& k, int ld_dy) {
-  const bool direct = d->ntaps == 1 && k.stride == 1 && k.mode == DMC_MODE_NORMAL && k.tdy0 == 0 && k.tdx0 == 0 &&
+// The 1x1 kind (wgrad1x1_glds_kernel) applies: 1x1 stride-1 bf16 (Linear-shaped), whole 64-pixel stages, 8-aligned
+// channels and pitches, a second source only behind a 128-aligned first one, 32-bit buffer offsets
+bool wg1x1_ok(const ConvK& k, int ld_dy) {
+  const bool direct = k.ntaps == 1 && k.stride == 1 && k.mode == DMC_MODE_NORMAL && k.tdy0 == 0 && k.tdx0 == 0 &&
                       k.H == k.OH && k.W == k.OW && k.prologue == DMC_PRO_NONE;
-  return d->dtype == DMC_BF16 && direct && k.M % 64 == 0 && d->Cout % 8 == 0 && ld_dy % 8 == 0 && k.C1 % 8 == 0 &&
+  return k.dtype_bytes == 2 && direct && k.M % 64 == 0 && k.Cout % 8 == 0 && ld_dy % 8 == 0 && k.C1 % 8 == 0 &&
          k.C2 % 8 == 0 && (k.C2 == 0 || k.C1 % 128 == 0) && k.ld1 % 8 == 0 && (k.C2 == 0 || k.ld2 % 8 == 0) &&
-         k.x1_bytes > 0 && (k.C2 == 0 || k.x2_bytes > 0) && (size_t)k.M * ld_dy * 2 < 0x7fff0000u;
+         k.x1_bytes > 0 && (k.C2 == 0 || k.x2_bytes > 0) && wg_dy_fits(k, ld_dy);
 }
 
 // Pixels per split of a single 1x1 layer: one round of blocks (two per CU: <= 512, e.g. 504 not 516 for the 16x16
 // qkv's 12 tiles -- a 4-block second round cost 24 %) and >= 256 pixels per block (fewer, longer splits on the 8x8 /
 // 4x4 maps): the block-count sweep's per-shape optimum within ~4 % (scripts/wgrad_sweep.py --only 1x1, round 5);
-// whole 64-pixel stages, never more splits than wgrad_splits() counted (the workspace query's bound)
-int wg1x1_single_pps(const dmc_conv_desc* d) {
-  int pps;
-  const int ws_splits = wgrad_splits(d, &pps);
-  const int M = d->N * d->OH * d->OW;
-  const long tiles = (long)dmc::cdiv(d->Kc, 128) * dmc::cdiv(d->Cout, 128);
-  long sp = std::min(512 / tiles, (long)M / 256);
-  if (sp > ws_splits) sp = ws_splits;
-  if (sp < 1) sp = 1;
-  return dmc::cdiv(dmc::cdiv(M, (int)sp), 64) * 64;
+// whole 64-pixel stages, never more splits than the generic kernel would get (what the workspace query counts)
+int wg1x1_pps(const ConvK& k, long tiles, int generic_splits) {
+  const long sp = std::max(1L, std::min(std::min(512 / tiles, (long)k.M / 256), (long)generic_splits));
+  return dmc::cdiv(dmc::cdiv(k.M, (int)sp), 64) * 64;
 }
 
-Wg1x1Job wg1x1_job(const ConvK& k, const dmc_conv_desc* d, const void* dy, int ld_dy, float* slab, float* wgb) {
-  Wg1x1Job j;
-  j.x1 = k.x1; j.x2 = k.x2; j.dy = (const char*)dy;
-  j.slab = slab; j.wgb = wgb;
-  j.x1_bytes = k.x1_bytes; j.x2_bytes = k.x2_bytes; j.dy_bytes = (int)((size_t)k.M * ld_dy * 2);
-  j.ld1 = k.ld1; j.ld2 = k.ld2; j.ld_dy = ld_dy;
-  j.C1 = k.C1; j.C2 = k.C2; j.Cout = k.Cout; j.M = k.M;
-  j.nci = dmc::cdiv(d->Kc, 128); j.nco = dmc::cdiv(d->Cout, 128);
-  return j;
+// PIPE / GEMM1X1: cut the job's work `per` units at a time. The slab is dw-shaped and the bias partials follow it
+// directly (the grouped entry's layout; plan_wgrad moves them for a single-layer call).
+void wg_set_split(WgPlan& p, int per) {
+  p.per = per;
+  p.splits = dmc::cdiv(p.units, per);
+  p.grid = dim3((unsigned)(p.base * p.splits));
+  p.slab_floats = (size_t)p.splits * p.k.Cout * (p.k.C1 + p.k.C2) * p.k.ntaps;
+  p.bias_off = p.slab_floats;
 }
 
-void wg_pipe_launch(int ow, const WgPipeGroup& grp, hipStream_t s) {
-  const dim3 g1(grp.first[grp.njobs]);
-  if (ow == 32) wgrad3x3_pipe_kernel<32><<<g1, 512, 0, s>>>(grp);
-  else if (ow == 16) wgrad3x3_pipe_kernel<16><<<g1, 512, 0, s>>>(grp);
-  else if (ow == 8) wgrad3x3_pipe_kernel<8><<<g1, 512, 0, s>>>(grp);
-  else wgrad3x3_pipe_kernel<4><<<g1, 512, 0, s>>>(grp);
-}
-
-// Plan of a grouped launch sequence (dmc_conv2d_wgrad_group): consecutive jobs share a launch while their output tiles
-// (base = ci chunks x co tiles) stay within a quarter of the one-round block target, and a launch's jobs share one
-// tiles-per-split: the smallest for which sum_j base_j * ceil(ntiles_j / tps) stays within the target (of one job:
-// wgrad_pipe_plan's).
-// The 1x1 kind (wgrad1x1_glds_kernel) is planned the same way in its own units: 128 x 128 output tiles, one shared
-// pixels-per-split (whole 64-pixel stages, >= 256 pixels as in the single-layer plan), a block target of 512.
-constexpr int kWgKind1x1 = 1;
-struct WgGroupPlan {
-  int ow;                       // map width of the 3x3 kind, kWgKind1x1, or 0: not a group (a job is not eligible,
-                                // or the kinds / map widths differ)
-  int nlaunch;
-  int lfirst[kWgGroup + 1];     // launch l runs jobs [lfirst[l], lfirst[l + 1])
-  int tps[kWgGroup];            // per launch: tiles per split (3x3) / pixels per split (1x1)
-  int splits[kWgGroup];         // per job
-};
-// 32 / 16 / 8: the pipelined 3x3 kernel on that map width; kWgKind1x1; 0: not eligible
-int wg_group_kind(const dmc_conv_desc* d, int ld_dy) {
-  if (d->ntaps == 1) {
-    ConvK k;
-    if (d->dtype != DMC_BF16 || fill_convk(d, nullptr, nullptr, nullptr, nullptr, nullptr, k)) return 0;
-    return wg1x1_ok(d, k, ld_dy) ? kWgKind1x1 : 0;
+WgPlan plan_wgrad(const dmc_conv_desc* d, int ld_dy) {
+  WgPlan p{};
+  ConvK& k = p.k;
+  if (fill_convk(d, nullptr, nullptr, nullptr, nullptr, nullptr, k)) return p;
+  if (ld_dy % (d->dtype == DMC_F32 ? 4 : 8)) {
+    dmc::set_error("wgrad: ld_dy %d alignment", ld_dy);
+    return p;
   }
-  const int ow = wgrad_pipe_plan(d, ld_dy).ow;
-  return ow == 32 || ow == 16 || ow == 8 ? ow : 0;
-}
-WgGroupPlan wg_group_plan(const dmc_wgrad_group_item* it, int n) {
-  WgGroupPlan p{};
-  long base[kWgGroup];
-  int ntiles[kWgGroup];
-  for (int i = 0; i < n; ++i) {
-    const dmc_conv_desc* d = it[i].d;
-    const int kind = wg_group_kind(d, it[i].ld_dy);
-    if (!kind || (i && kind != p.ow)) { p.ow = 0; return p; }
-    p.ow = kind;
-    if (kind == kWgKind1x1) {
-      base[i] = (long)dmc::cdiv(d->Kc, 128) * dmc::cdiv(d->Cout, 128);
-      ntiles[i] = d->N * d->OH * d->OW / 64;   // 64-pixel stages
-    } else {
-      base[i] = (long)(d->Kc / 64) * dmc::cdiv(d->Cout, 64);
-      ntiles[i] = d->N * d->OH * d->OW / 128;
-    }
+  p.ok = true;
+  p.ld_dy = ld_dy;
+  p.block = 256;
+  p.Cpad = dmc::cdiv(k.Cout, 128) * 128;
+  const int KK = k.ntaps * k.Kc;
+  if (wg_img4_ok(k, ld_dy)) {
+    p.kind = DMC_WGRAD_IMG4;
+    p.grid = dim3((k.Cout / 16) * ((k.C1 + k.C2) / 16));
+    return p;
   }
-  const bool k1 = p.ow == kWgKind1x1;
-  const long target = k1 ? 512 : dmc::opt(dmc::OPT_WG_HALO_TARGET);
-  int i = 0;
-  while (i < n) {
-    int e = i + 1;
-    long sum = base[i];
-    // at most target / 4 output tiles per launch: with one tiles-per-split the launch runs sum x floor(target / sum)
-    // blocks, and every job is split at least 4 times, so >= 80 % of the block target is used (four decoder jobs of
-    // 16 + 32 + 16 + 32 tiles would run 96 x 2 = 192 blocks of 256: measured slower than ungrouped)
-    const long cap = std::max(target / 4, 1L);
-    while (e < n && sum + base[e] <= cap) sum += base[e++];
-    int maxt = 1;
-    for (int j = i; j < e; ++j) maxt = std::max(maxt, ntiles[j]);
-    int tps = k1 ? std::min(4, maxt) : 1;   // 1x1: at least 256 pixels per split
-    for (; tps < maxt; ++tps) {
-      long blocks = 0;
-      for (int j = i; j < e; ++j) blocks += base[j] * dmc::cdiv(ntiles[j], tps);
-      if (blocks <= target) break;
-    }
-    // a 1x1 launch of one job: the single-layer plan, so that it is bitwise dmc_conv2d_wgrad_partial (for 3x3 the
-    // search above already is wgrad_pipe_plan's)
-    if (k1 && e == i + 1) tps = wg1x1_single_pps(it[i].d) / 64;
-    for (int j = i; j < e; ++j) p.splits[j] = dmc::cdiv(ntiles[j], tps);
-    p.tps[p.nlaunch] = k1 ? tps * 64 : tps;
-    p.lfirst[p.nlaunch++] = i;
-    i = e;
+  int generic_pps;
+  const int generic_splits = wgrad_splits(d, &generic_pps);
+  if (wg_pipe_fits(k, ld_dy, p)) {
+    p.kind = DMC_WGRAD_PIPE;
+    p.block = 512;
+    p.layout = 1;
+    wg_set_split(p, p.per);
+  } else if (wg_dy_fits(k, ld_dy) && wg_halo_fits(k, p)) {
+    // two blocks per CU: 64-co blocks, the same split count (twice the co tiles, half the block target's share)
+    p.kind = DMC_WGRAD_HALO;
+    p.grid = dim3(k.Kc / 64, dmc::cdiv(k.Cout, 64), p.splits);
+  } else if (wg1x1_ok(k, ld_dy)) {
+    p.kind = DMC_WGRAD_GEMM1X1;
+    p.layout = 1;
+    p.units = k.M;
+    p.base = (long)dmc::cdiv(k.Kc, 128) * dmc::cdiv(k.Cout, 128);
+    wg_set_split(p, wg1x1_pps(k, p.base, generic_splits));
+  } else {
+    p.kind = DMC_WGRAD_GENERIC;
+    p.splits = generic_splits;
+    p.per = generic_pps;
+    p.grid = dim3(dmc::cdiv(KK, 128), dmc::cdiv(k.Cout, 128), p.splits);
   }
-  p.lfirst[p.nlaunch] = n;
+  if (!p.layout) p.slab_floats = (size_t)p.splits * KK * p.Cpad;
+  // a single-layer call keeps the bias partials behind a layout-0 sized slab whatever the layout
+  p.bias_off = (size_t)p.splits * KK * p.Cpad;
   return p;
 }
-// bytes of job i's workspace: the dw-shaped slab of its splits, then the bias partials [splits][Cpad]
-size_t wg_group_bytes(const dmc_conv_desc* d, int splits) {
-  const size_t Cpad = (size_t)dmc::cdiv(d->Cout, 128) * 128;
-  return (size_t)splits * ((size_t)d->Cout * (d->C1 + d->C2) * d->ntaps + Cpad) * sizeof(float);
+
+// What dmc_conv2d_wgrad_group_ok answers: the map width (32 / 16 / 8) of the pipelined kind, kWgKind1x1, or 0: the
+// grouped entry does not take the job (width 4 is pipelined only as a single call: DESIGN.md, quirk 4)
+constexpr int kWgKind1x1 = 1;
+int wg_group_kind(const WgPlan& p) {
+  if (!p.ok) return 0;
+  if (p.kind == DMC_WGRAD_GEMM1X1) return kWgKind1x1;
+  return p.kind == DMC_WGRAD_PIPE && p.ow != 4 ? p.ow : 0;
 }
 
+// Plan of a grouped launch sequence (dmc_conv2d_wgrad_group), from the jobs' own plans: consecutive jobs share a launch
+// while their output tiles (base) stay within a quarter of the one-round block target, and a launch's jobs share one
+// `per`: the smallest for which sum_j base_j * ceil(units_j / per) stays within the target. A launch of one job keeps
+// the job's own split, so it is bitwise the single-layer call (for the 3x3 kind the search would find the same).
+// The 1x1 kind is planned in its own units: 128 x 128 output tiles, pixels per split in whole 64-pixel stages, >= 256
+// pixels as in the single-layer plan, a block target of 512.
+struct WgGroupPlan {
+  int kind;                     // wg_group_kind of every job, or 0: not a group (a job is not eligible, or they differ)
+  int nlaunch;
+  int lfirst[kWgGroup + 1];     // launch l runs jobs [lfirst[l], lfirst[l + 1])
+  WgPlan job[kWgGroup];         // split as the group runs them
+};
+void wg_group_plan(const dmc_wgrad_group_item* it, int n, WgGroupPlan& g) {
+  g.kind = g.nlaunch = 0;
+  for (int i = 0; i < n; ++i) {
+    g.job[i] = plan_wgrad(it[i].d, it[i].ld_dy);
+    const int kind = wg_group_kind(g.job[i]);
+    if (!kind || (i && kind != g.kind)) { g.kind = 0; return; }
+    g.kind = kind;
+  }
+  const bool k1 = g.kind == kWgKind1x1;
+  const int stage = k1 ? 64 : 1;   // the search counts the 1x1 kind's pixels in 64-pixel stages
+  const long target = k1 ? 512 : dmc::opt(dmc::OPT_WG_HALO_TARGET);
+  // at most target / 4 output tiles per launch: with one tiles-per-split the launch runs sum x floor(target / sum)
+  // blocks, and every job is split at least 4 times, so >= 80 % of the block target is used (four decoder jobs of
+  // 16 + 32 + 16 + 32 tiles would run 96 x 2 = 192 blocks of 256: measured slower than ungrouped)
+  const long cap = std::max(target / 4, 1L);
+  for (int i = 0, e; i < n; i = e) {
+    e = i + 1;
+    long sum = g.job[i].base;
+    while (e < n && sum + g.job[e].base <= cap) sum += g.job[e++].base;
+    int per = g.job[i].per;
+    if (e > i + 1) {
+      int maxt = 1;
+      for (int j = i; j < e; ++j) maxt = std::max(maxt, g.job[j].units / stage);
+      int tps = k1 ? std::min(4, maxt) : 1;   // 1x1: at least 256 pixels per split
+      for (; tps < maxt; ++tps) {
+        long blocks = 0;
+        for (int j = i; j < e; ++j) blocks += g.job[j].base * dmc::cdiv(g.job[j].units / stage, tps);
+        if (blocks <= target) break;
+      }
+      per = tps * stage;
+    }
+    for (int j = i; j < e; ++j) wg_set_split(g.job[j], per);
+    g.lfirst[g.nlaunch++] = i;
+  }
+  g.lfirst[g.nlaunch] = n;
+}
+// bytes of a grouped job's workspace: the dw-shaped slab of its splits, then the bias partials [splits][Cpad]
+size_t wg_group_bytes(const WgPlan& p) { return (p.slab_floats + (size_t)p.splits * p.Cpad) * sizeof(float); }
+
 std::atomic<long> g_slab_bytes{0};   // dmc_wgrad_slab_bytes
+
+// The reduction that finishes a planned job (and the one place that counts its slab); returns the bias partials
+float* wg_fill_job(const WgPlan& p, const dmc_wgrad_group_item& I, dmc_wgrad_job* J) {
+  float* const slab = (float*)I.workspace;
+  float* const bslab = I.d->wg_bias ? slab + p.bias_off : nullptr;
+  *J = dmc_wgrad_job{};
+  J->slab = slab; J->bslab = bslab; J->dw = I.dw; J->dbias = I.d->wg_bias;
+  J->splits = p.splits; J->KK = p.k.ntaps * p.k.Kc; J->Cpad = p.Cpad; J->Cout = p.k.Cout;
+  J->Ctot = p.k.C1 + p.k.C2; J->ntaps = p.k.ntaps; J->Kc = p.k.Kc; J->scale = I.scale; J->layout = p.layout;
+  g_slab_bytes += (long)(p.slab_floats * sizeof(float));
+  return bslab;
+}
+
+// A job's entry in the by-value table of the pipelined / 1x1 kernel: each struct's own fields, and the shared ones
+void wg_table_extra(WgPipeJob& j, const WgPlan& p) {
+  j.H = p.k.H; j.OHW = p.k.OHW; j.ntiles = p.units;
+  j.ncb = p.k.Kc / 64; j.nob = dmc::cdiv(p.k.Cout, 64); j.Cpad = p.Cpad;
+}
+void wg_table_extra(Wg1x1Job& j, const WgPlan& p) {
+  j.M = p.k.M; j.nci = dmc::cdiv(p.k.Kc, 128); j.nco = dmc::cdiv(p.k.Cout, 128);
+}
+template <typename Job>
+void wg_table_job(Job& j, const WgPlan& p, const dmc_wgrad_group_item& I, float* wgb) {
+  const ConvK& k = p.k;
+  j.x1 = (const char*)I.x1; j.x2 = (const char*)I.x2; j.dy = (const char*)I.dy;
+  j.slab = (float*)I.workspace; j.wgb = wgb;
+  j.x1_bytes = k.x1_bytes; j.x2_bytes = k.x2_bytes; j.dy_bytes = (int)((size_t)k.M * p.ld_dy * 2);
+  j.ld1 = k.ld1; j.ld2 = k.ld2; j.ld_dy = p.ld_dy;
+  j.C1 = k.C1; j.C2 = k.C2; j.Cout = k.Cout;
+  wg_table_extra(j, p);
+}
+// the table of one launch and the jobs' reductions; returns the launch's block count
+template <typename Group>
+int wg_fill_group(Group& grp, const WgPlan* plans, const dmc_wgrad_group_item* items, int n, dmc_wgrad_job* jobs) {
+  grp.njobs = n;
+  int nb = 0;
+  for (int q = 0; q < n; ++q) {
+    grp.first[q] = nb;
+    wg_table_job(grp.j[q], plans[q], items[q], wg_fill_job(plans[q], items[q], &jobs[q]));
+    nb += (int)(plans[q].base * plans[q].splits);
+  }
+  grp.first[n] = nb;
+  return nb;
+}
+
+// One launch of the pipelined or the 1x1 kernel for n jobs of one kind (and map width) that share `per`
+int wg_launch_group(const WgPlan* plans, const dmc_wgrad_group_item* items, int n, dmc_wgrad_job* jobs, hipStream_t s,
+                    const char* what) {
+  if (plans[0].kind == DMC_WGRAD_GEMM1X1) {
+    Wg1x1Group grp{};
+    grp.pps = plans[0].per;
+    grp.xcd = dmc::opt(dmc::OPT_NO_XCD) ? 0 : 1;
+    const int nb = wg_fill_group(grp, plans, items, n, jobs);
+    wgrad1x1_glds_kernel<64, 2><<<dim3(nb), 256, 0, s>>>(grp);
+  } else {
+    WgPipeGroup grp{};
+    grp.tps = plans[0].per;
+    const dim3 g1(wg_fill_group(grp, plans, items, n, jobs));
+    const int ow = plans[0].ow;
+    if (ow == 32) wgrad3x3_pipe_kernel<32><<<g1, 512, 0, s>>>(grp);
+    else if (ow == 16) wgrad3x3_pipe_kernel<16><<<g1, 512, 0, s>>>(grp);
+    else if (ow == 8) wgrad3x3_pipe_kernel<8><<<g1, 512, 0, s>>>(grp);
+    else wgrad3x3_pipe_kernel<4><<<g1, 512, 0, s>>>(grp);
+  }
+  return dmc::check_launch(what);
+}
+
+// Runs the plan of a single-layer call: the partial sums into I.workspace, and in *job the reduction that finishes
+// them (dmc_conv2d_wgrad runs it at once, dmc_conv2d_wgrad_partial leaves it to the caller)
+int launch_wgrad(const WgPlan& p, const dmc_wgrad_group_item& I, dmc_wgrad_job* job, hipStream_t s) {
+  const char* const what = "dmc_conv2d_wgrad";
+  if (p.kind == DMC_WGRAD_PIPE || p.kind == DMC_WGRAD_GEMM1X1) return wg_launch_group(&p, &I, 1, job, s, what);
+  ConvK k = p.k;
+  k.x1 = (const char*)I.x1; k.x2 = (const char*)I.x2;
+  const char* const dy = (const char*)I.dy;
+  const int ld_dy = p.ld_dy, dyb = (int)((size_t)k.M * ld_dy * 2);
+  if (p.kind == DMC_WGRAD_IMG4) {
+    // the whole reduction inside the kernel: dw (and the bias gradient) written directly, no job left to reduce
+    if (I.d->wg_bias)
+      wgrad3x3_img4_kernel<true><<<p.grid, 256, 0, s>>>(k, dy, ld_dy, dyb, I.dw, I.d->wg_bias, I.scale);
+    else
+      wgrad3x3_img4_kernel<false><<<p.grid, 256, 0, s>>>(k, dy, ld_dy, dyb, I.dw, nullptr, I.scale);
+    *job = dmc_wgrad_job{};
+    return dmc::check_launch(what);
+  }
+  k.wgb = wg_fill_job(p, I, job);
+  float* const slab = (float*)I.workspace;
+  if (p.kind == DMC_WGRAD_HALO) {
+    if (p.hp == 6) wgrad3x3_halo2_kernel<6><<<p.grid, 256, 0, s>>>(k, dy, ld_dy, dyb, slab, p.R, p.nimg, p.per);
+    else wgrad3x3_halo2_kernel<7><<<p.grid, 256, 0, s>>>(k, dy, ld_dy, dyb, slab, p.R, p.nimg, p.per);
+  } else if (k.dtype_bytes == 4) {
+    conv_wgrad_kernel<float><<<p.grid, 256, 0, s>>>(k, dy, ld_dy, slab, k.ntaps * k.Kc, p.per);
+  } else {
+    conv_wgrad_kernel<bf16_t><<<p.grid, 256, 0, s>>>(k, dy, ld_dy, slab, k.ntaps * k.Kc, p.per);
+  }
+  return dmc::check_launch(what);
+}
 
 }  // namespace
 
@@ -1472,15 +1581,65 @@ extern "C" long dmc_wgrad_slab_bytes(int reset) {
   return reset ? g_slab_bytes.exchange(0) : g_slab_bytes.load();
 }
 
-extern "C" int dmc_conv2d_wgrad_group_ok(const dmc_conv_desc* d, int ld_dy) { return wg_group_kind(d, ld_dy); }
+// The largest slab over the plans the descriptor can get, always sized as layout 0 (splits x KK x Cpad, + the bias
+// partials [splits][Cpad]): the generic kernel's split count (which bounds the 1x1 kind's), the halo kind's, and the
+// pipelined kind's at a guessed dy pitch (Cout rounded up to 8: the query has no ld_dy). DESIGN.md, quirk 1.
+extern "C" size_t dmc_conv2d_wgrad_workspace(const dmc_conv_desc* d) {
+  int pps;
+  int splits = wgrad_splits(d, &pps);
+  WgPlan c{};
+  if (d->dtype == DMC_BF16 && !fill_convk(d, nullptr, nullptr, nullptr, nullptr, nullptr, c.k)) {
+    if (wg_halo_fits(c.k, c)) splits = std::max(splits, c.splits);
+    if (wg_pipe_fits(c.k, (d->Cout + 7) / 8 * 8, c)) splits = std::max(splits, dmc::cdiv(c.units, c.per));
+  }
+  const size_t KK = (size_t)d->ntaps * d->Kc;
+  const size_t Cpad = (size_t)dmc::cdiv(d->Cout, 128) * 128;
+  return (size_t)splits * (KK + 1) * Cpad * sizeof(float);
+}
+
+extern "C" int dmc_conv2d_wgrad_plan(const dmc_conv_desc* d, int ld_dy, dmc_wgrad_plan* out) {
+  DMC_REQUIRE(d && out, "wgrad_plan: arguments");
+  const WgPlan p = plan_wgrad(d, ld_dy);
+  if (!p.ok) return 1;
+  *out = dmc_wgrad_plan{};
+  out->kind = p.kind;
+  out->grid[0] = p.grid.x; out->grid[1] = p.grid.y; out->grid[2] = p.grid.z;
+  out->block = p.block;
+  out->splits = p.splits;
+  out->layout = p.layout;
+  out->group_kind = wg_group_kind(p);
+  out->ws_bytes = dmc_conv2d_wgrad_workspace(d);
+  return 0;
+}
+
+extern "C" int dmc_conv2d_wgrad_partial(const dmc_conv_desc* d, const void* dy, int ld_dy, const void* x1,
+                                        const void* x2, void* workspace, float* dw, float scale, dmc_wgrad_job* job,
+                                        void* stream) {
+  DMC_REQUIRE(job != nullptr, "wgrad_partial: job");
+  const WgPlan p = plan_wgrad(d, ld_dy);
+  if (!p.ok) return 1;
+  return launch_wgrad(p, dmc_wgrad_group_item{d, dy, ld_dy, x1, x2, workspace, dw, scale}, job, dmc::as_stream(stream));
+}
+
+extern "C" int dmc_conv2d_wgrad(const dmc_conv_desc* d, const void* dy, int ld_dy, const void* x1, const void* x2,
+                                void* workspace, float* dw, float scale, void* stream) {
+  dmc_wgrad_job job;
+  const int r = dmc_conv2d_wgrad_partial(d, dy, ld_dy, x1, x2, workspace, dw, scale, &job, stream);
+  return r ? r : dmc_wgrad_reduce_batch(&job, 1, stream);
+}
+
+extern "C" int dmc_conv2d_wgrad_group_ok(const dmc_conv_desc* d, int ld_dy) {
+  return wg_group_kind(plan_wgrad(d, ld_dy));
+}
 
 extern "C" size_t dmc_conv2d_wgrad_group_workspace(const dmc_wgrad_group_item* items, int njobs, size_t* bytes) {
   if (njobs < 1 || njobs > kWgGroup || !items) return 0;
-  const WgGroupPlan p = wg_group_plan(items, njobs);
-  if (!p.ow) return 0;
+  WgGroupPlan g;
+  wg_group_plan(items, njobs, g);
+  if (!g.kind) return 0;
   size_t total = 0;
   for (int i = 0; i < njobs; ++i) {
-    const size_t b = wg_group_bytes(items[i].d, p.splits[i]);
+    const size_t b = wg_group_bytes(g.job[i]);
     if (bytes) bytes[i] = b;
     total += b;
   }
@@ -1489,169 +1648,17 @@ extern "C" size_t dmc_conv2d_wgrad_group_workspace(const dmc_wgrad_group_item* i
 
 extern "C" int dmc_conv2d_wgrad_group(const dmc_wgrad_group_item* items, int njobs, dmc_wgrad_job* jobs, void* stream) {
   DMC_REQUIRE(items && jobs && njobs >= 1 && njobs <= kWgGroup, "wgrad_group: %d jobs (1..%d)", njobs, kWgGroup);
-  const WgGroupPlan p = wg_group_plan(items, njobs);
-  DMC_REQUIRE(p.ow != 0, "wgrad_group: every job must be a bf16 3x3 stride-1 conv of one map width (32, 16 or 8), or "
-                         "every job a bf16 1x1 stride-1 conv");
-  hipStream_t s = dmc::as_stream(stream);
-  const bool k1 = p.ow == kWgKind1x1;
-  for (int l = 0; l < p.nlaunch; ++l) {
-    WgPipeGroup grp{};
-    Wg1x1Group grp1{};
-    grp.njobs = grp1.njobs = p.lfirst[l + 1] - p.lfirst[l];
-    grp.tps = grp1.pps = p.tps[l];
-    grp1.xcd = dmc::opt(dmc::OPT_NO_XCD) ? 0 : 1;
-    int nb = 0;
-    for (int i = p.lfirst[l]; i < p.lfirst[l + 1]; ++i) {
-      const dmc_wgrad_group_item& I = items[i];
-      const dmc_conv_desc* d = I.d;
-      DMC_REQUIRE(I.dy && I.x1 && I.workspace && I.dw, "wgrad_group: job %d pointers", i);
-      ConvK k;
-      if (fill_convk(d, I.x1, I.x2, nullptr, nullptr, nullptr, k)) return 1;
-      const int splits = p.splits[i], Ctot = d->C1 + d->C2;
-      float* const slab = (float*)I.workspace;
-      float* const bslab = d->wg_bias ? slab + (size_t)splits * d->Cout * Ctot * d->ntaps : nullptr;
-      const int q = i - p.lfirst[l];
-      grp.first[q] = grp1.first[q] = nb;
-      if (k1) {
-        grp1.j[q] = wg1x1_job(k, d, I.dy, I.ld_dy, slab, bslab);
-        nb += grp1.j[q].nci * grp1.j[q].nco * splits;
-      } else {
-        grp.j[q] = wg_pipe_job(k, d, I.dy, I.ld_dy, slab, bslab);
-        nb += grp.j[q].ncb * grp.j[q].nob * splits;
-      }
-      dmc_wgrad_job& J = jobs[i];
-      J = dmc_wgrad_job{};
-      J.slab = slab; J.bslab = bslab; J.dw = I.dw; J.dbias = d->wg_bias;
-      J.splits = splits; J.KK = d->ntaps * d->Kc; J.Cpad = dmc::cdiv(d->Cout, 128) * 128; J.Cout = d->Cout;
-      J.Ctot = Ctot; J.ntaps = d->ntaps; J.Kc = d->Kc; J.scale = I.scale; J.layout = 1;
-      g_slab_bytes += (long)((size_t)splits * d->Cout * Ctot * d->ntaps * sizeof(float));
-    }
-    grp.first[grp.njobs] = grp1.first[grp.njobs] = nb;
-    if (k1) wgrad1x1_glds_kernel<64, 2><<<dim3(nb), 256, 0, s>>>(grp1);
-    else wg_pipe_launch(p.ow, grp, s);
-    if (dmc::check_launch("dmc_conv2d_wgrad_group")) return 2;
+  WgGroupPlan g;
+  wg_group_plan(items, njobs, g);
+  DMC_REQUIRE(g.kind != 0, "wgrad_group: every job must be a bf16 3x3 stride-1 conv of one map width (32, 16 or 8), or "
+                           "every job a bf16 1x1 stride-1 conv");
+  for (int l = 0; l < g.nlaunch; ++l) {
+    const int i0 = g.lfirst[l], n = g.lfirst[l + 1] - i0;
+    for (int i = i0; i < i0 + n; ++i)
+      DMC_REQUIRE(items[i].dy && items[i].x1 && items[i].workspace && items[i].dw, "wgrad_group: job %d pointers", i);
+    if (wg_launch_group(g.job + i0, items + i0, n, jobs + i0, dmc::as_stream(stream), "dmc_conv2d_wgrad_group")) return 2;
   }
   return 0;
-}
-
-extern "C" size_t dmc_conv2d_wgrad_workspace(const dmc_conv_desc* d) {
-  int pps;
-  int splits = wgrad_splits(d, &pps);
-  const WgHaloPlan hp = wgrad_halo_plan(d);
-  if (hp.ok && hp.splits > splits) splits = hp.splits;
-  const WgPipePlan pp = wgrad_pipe_plan(d, ((d->Cout + 7) / 8) * 8);
-  if (pp.ow && pp.splits > splits) splits = pp.splits;
-  const size_t KK = (size_t)d->ntaps * d->Kc;
-  const size_t Cpad = (size_t)dmc::cdiv(d->Cout, 128) * 128;
-  return (size_t)splits * (KK + 1) * Cpad * sizeof(float);   // + the bias partials [splits][Cpad]
-}
-
-// Launches the weight-gradient kernel of `d` (partial sums into the workspace slab) and describes the reduction
-// that finishes it in *job (dmc_conv2d_wgrad runs it at once, dmc_conv2d_wgrad_partial leaves it to the caller).
-static int wgrad_partial(const dmc_conv_desc* d, const void* dy, int ld_dy, const void* x1, const void* x2,
-                         void* workspace, float* dw, float scale, dmc_wgrad_job* job, void* stream) {
-  ConvK k;
-  if (fill_convk(d, x1, x2, nullptr, nullptr, nullptr, k)) return 1;
-  const int epc = d->dtype == DMC_F32 ? 4 : 8;
-  DMC_REQUIRE(ld_dy % epc == 0, "wgrad: ld_dy %d alignment", ld_dy);
-  hipStream_t s = dmc::as_stream(stream);
-  if (wgrad_img4_ok(d, k, ld_dy)) {
-    // the whole reduction inside the kernel: dw (and the bias gradient) written directly, no job left to reduce
-    const int nb = (d->Cout / 16) * ((k.C1 + k.C2) / 16), dyb = (int)((size_t)k.M * ld_dy * 2);
-    if (d->wg_bias)
-      wgrad3x3_img4_kernel<true><<<nb, 256, 0, s>>>(k, (const char*)dy, ld_dy, dyb, dw, d->wg_bias, scale);
-    else
-      wgrad3x3_img4_kernel<false><<<nb, 256, 0, s>>>(k, (const char*)dy, ld_dy, dyb, dw, nullptr, scale);
-    if (dmc::check_launch("dmc_conv2d_wgrad")) return 2;
-    *job = dmc_wgrad_job{};
-    job->splits = 0;
-    return 0;
-  }
-  int pps;
-  int splits = wgrad_splits(d, &pps);
-  const int KK = d->ntaps * d->Kc;
-  dim3 g(dmc::cdiv(KK, 128), dmc::cdiv(d->Cout, 128), splits);
-  const WgHaloPlan hp = wgrad_halo_plan(d);
-  const size_t dyb = (size_t)k.M * ld_dy * 2;
-  const WgPipePlan pp = wgrad_pipe_plan(d, ld_dy);
-  const bool halo = !pp.ow && hp.ok && dyb < 0x7fff0000u;
-  if (halo) splits = hp.splits;
-  if (pp.ow) splits = pp.splits;
-  // 1x1 stride-1 bf16 (Linear-shaped): both operands DMA'd into LDS (wgrad1x1_glds_kernel); splits are whole
-  // SPX-pixel stages, never more than wgrad_splits() counted (the workspace query's bound)
-  const bool w1x1 = !halo && wg1x1_ok(d, k, ld_dy);
-  int pps1 = 0;
-  if (w1x1) {
-    pps1 = wg1x1_single_pps(d);
-    splits = dmc::cdiv(k.M, pps1);
-  }
-  const size_t Cpad = (size_t)dmc::cdiv(d->Cout, 128) * 128;
-  // bias partials after the weight slab (dmc_conv2d_wgrad_workspace sized for the larger split count)
-  float* const bslab = d->wg_bias ? (float*)workspace + (size_t)splits * KK * Cpad : nullptr;
-  k.wgb = bslab;
-  if (pp.ow) {
-    // a group of one job: the single-conv plan (the grouped entry's plan of one job is the same)
-    WgPipeGroup grp{};
-    grp.njobs = 1;
-    grp.tps = pp.tps;
-    grp.j[0] = wg_pipe_job(k, d, dy, ld_dy, (float*)workspace, bslab);
-    grp.first[0] = 0;
-    grp.first[1] = grp.j[0].ncb * grp.j[0].nob * splits;
-    wg_pipe_launch(pp.ow, grp, s);
-    g.y = dmc::cdiv(d->Cout, 128);   // the reduce's slab pitch: Cout rounded to 128
-  } else if (halo) {
-    // two blocks per CU: 64-co blocks, the same split count (twice the co tiles, half the block target's share)
-    g = dim3(d->Kc / 64, dmc::cdiv(d->Cout, 64), splits);
-    if (hp.hp == 6)
-      wgrad3x3_halo2_kernel<6><<<g, 256, 0, s>>>(k, (const char*)dy, ld_dy, (int)dyb, (float*)workspace, hp.R, hp.nimg, hp.tps);
-    else
-      wgrad3x3_halo2_kernel<7><<<g, 256, 0, s>>>(k, (const char*)dy, ld_dy, (int)dyb, (float*)workspace, hp.R, hp.nimg, hp.tps);
-    g.y = dmc::cdiv(d->Cout, 128);   // the reduce's slab pitch: Cout rounded to 128
-  } else if (w1x1) {
-    g.z = splits;
-    Wg1x1Group grp{};   // a group of one job
-    grp.njobs = 1;
-    grp.pps = pps1;
-    grp.xcd = dmc::opt(dmc::OPT_NO_XCD) ? 0 : 1;
-    grp.j[0] = wg1x1_job(k, d, dy, ld_dy, (float*)workspace, bslab);
-    grp.first[0] = 0;
-    grp.first[1] = (int)(g.x * g.y * g.z);
-    wgrad1x1_glds_kernel<64, 2><<<dim3(grp.first[1]), 256, 0, s>>>(grp);
-  } else if (d->dtype == DMC_F32)
-    conv_wgrad_kernel<float><<<g, 256, 0, s>>>(k, (const char*)dy, ld_dy, (float*)workspace, KK, pps);
-  else
-    conv_wgrad_kernel<bf16_t><<<g, 256, 0, s>>>(k, (const char*)dy, ld_dy, (float*)workspace, KK, pps);
-  if (dmc::check_launch("dmc_conv2d_wgrad")) return 2;
-  job->slab = (const float*)workspace;
-  job->bslab = bslab;
-  job->dw = dw;
-  job->dbias = d->wg_bias;
-  job->splits = splits;
-  job->KK = KK;
-  job->Cpad = (int)g.y * 128;
-  job->Cout = d->Cout;
-  job->Ctot = d->C1 + d->C2;
-  job->ntaps = d->ntaps;
-  job->Kc = d->Kc;
-  job->scale = scale;
-  job->layout = (pp.ow || w1x1) ? 1 : 0;   // the pipelined 3x3 and the 1x1 kernels write dw-shaped slabs
-  g_slab_bytes += (long)((size_t)splits * (job->layout ? (size_t)job->Cout * job->Ctot * job->ntaps : KK * Cpad) *
-                         sizeof(float));
-  return 0;
-}
-
-extern "C" int dmc_conv2d_wgrad_partial(const dmc_conv_desc* d, const void* dy, int ld_dy, const void* x1,
-                                        const void* x2, void* workspace, float* dw, float scale, dmc_wgrad_job* job,
-                                        void* stream) {
-  DMC_REQUIRE(job != nullptr, "wgrad_partial: job");
-  return wgrad_partial(d, dy, ld_dy, x1, x2, workspace, dw, scale, job, stream);
-}
-
-extern "C" int dmc_conv2d_wgrad(const dmc_conv_desc* d, const void* dy, int ld_dy, const void* x1, const void* x2,
-                                void* workspace, float* dw, float scale, void* stream) {
-  dmc_wgrad_job job;
-  const int r = wgrad_partial(d, dy, ld_dy, x1, x2, workspace, dw, scale, &job, stream);
-  return r ? r : dmc_wgrad_reduce_batch(&job, 1, stream);
 }
 
 extern "C" int dmc_wgrad_reduce_batch(const dmc_wgrad_job* jobs_in, int njobs_in, void* stream) {

@@ -297,6 +297,14 @@ def wgrad_slab_bytes(reset=False):
     return LIB.dmc_wgrad_slab_bytes(int(reset))
 
 
+def wgrad_plan(d, ld_dy):
+    """include/dmc.h dmc_conv2d_wgrad_plan: the launch plan (L.WgradPlan) wgrad() follows for `d` and a dy pitch of
+    ld_dy. Host only."""
+    p = L.WgradPlan()
+    check(LIB.dmc_conv2d_wgrad_plan(ctypes.byref(d), ld_dy, ctypes.byref(p)), "dmc_conv2d_wgrad_plan")
+    return p
+
+
 def wgrad_group(items, defer=None):
     """dmc_conv2d_wgrad_group: the partial-sum kernels of up to 8 eligible 3x3 weight gradients of one map width, or of
     up to 8 eligible 1x1 ones, in shared launches. items: (d, dy, ld_dy, x1, x2, dw, scale, dbias) each. With defer (a WgradDefer) the reductions

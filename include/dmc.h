@@ -172,6 +172,26 @@ typedef struct dmc_wgrad_job {
 int dmc_conv2d_wgrad_partial(const dmc_conv_desc* d, const void* dy, int ld_dy, const void* x1, const void* x2,
                              void* workspace, float* dw, float scale, dmc_wgrad_job* job, void* stream);
 int dmc_wgrad_reduce_batch(const dmc_wgrad_job* jobs, int njobs, void* stream);
+/* The launch plan dmc_conv2d_wgrad / dmc_conv2d_wgrad_partial(d, dy, ld_dy, ...) follow, computed on the host without
+ * touching a device: the kernel kind, the main launch, the split count (0: the kernel reduces itself, the returned job
+ * is empty) and the slab layout of the returned job. group_kind is what dmc_conv2d_wgrad_group_ok(d, ld_dy) answers,
+ * ws_bytes what dmc_conv2d_wgrad_workspace(d) answers: reads of the same plan. Returns nonzero (dmc_last_error) where
+ * dmc_conv2d_wgrad would reject the descriptor or ld_dy. */
+enum { DMC_WGRAD_IMG4 = 1,       /* whole-image 4x4 3x3: no slab, no reduction */
+       DMC_WGRAD_PIPE = 2,       /* pipelined 3x3 on 32 / 16 / 8 / 4-wide maps */
+       DMC_WGRAD_HALO = 3,       /* 256-pixel halo 3x3 */
+       DMC_WGRAD_GEMM1X1 = 4,    /* LDS-DMA 1x1 / Linear */
+       DMC_WGRAD_GENERIC = 5 };  /* register-staged, everything else */
+typedef struct dmc_wgrad_plan {
+  int kind;                  /* DMC_WGRAD_* */
+  unsigned grid[3];          /* grid (blocks) and block size (threads) of the partial-sum launch */
+  int block;
+  int splits;
+  int layout;                /* dmc_wgrad_job.layout */
+  int group_kind;
+  size_t ws_bytes;
+} dmc_wgrad_plan;
+int dmc_conv2d_wgrad_plan(const dmc_conv_desc* d, int ld_dy, dmc_wgrad_plan* out);
 
 /* Grouped weight gradients: the partial-sum kernels of up to DMC_WGRAD_GROUP_MAX convs in shared launches. Every
  * job must be one dmc_conv2d_wgrad_group_ok accepts: bf16, and either 3x3 stride 1 with the forward taps, maps 32, 16
