@@ -177,6 +177,8 @@ def _load():
                                    _c_p, _c_p, _c_p]),
         "dmc_dpm_step": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p,
                                   _c_p]),
+        "dmc_known_blend": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p,
+                                     _c_p]),
         "dmc_cfg_x0": (_c_int, [_c_p, _c_p, _c_p, _c_f, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_f, _c_p, _c_p,
                                 _c_p]),
         "dmc_ema_update": (_c_int, [_c_p, _c_int, _c_f, _c_p]),

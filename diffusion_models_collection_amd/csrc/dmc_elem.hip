@@ -495,6 +495,72 @@ __global__ __launch_bounds__(256) void dpm_step_kernel(const float* x, const flo
   }
 }
 
+// Known-region blend for editing samplers: inpainting as RePaint (Lugmayr et al. 2022, arXiv:2201.09865, algorithm 1:
+// the known region is the given image noised to the step's target level, the rest the sampler's own output, and a
+// resampling repetition jumps forward again) and the start of SDEdit's image-to-image (Meng et al. 2021,
+// arXiv:2108.01073). diffusion/_edit.py builds the coefficient rows on the host, so nothing here is transcendental.
+// One element: the noised known value, the blend, and the re-noise only where the row has one; every op is a separate
+// rounding.
+struct BlendRow {
+  float ka, kb, ra, rb;
+};
+
+DMC_DEV float blend_elem(const BlendRow& r, float x, float x0, float m, float z, float z2) {
+  float known = r.ka * x0;
+  if (r.kb != 0.f) known = known + r.kb * z;
+  const float u = m * known;
+  const float w = (1.0f - m) * x;
+  float b = u + w;
+  if (r.rb != 0.f) {
+    const float p = r.ra * b;
+    b = p + r.rb * z2;
+  }
+  return b;
+}
+
+// Grid as dpm_step_kernel: blockIdx.y strides over samples, blockIdx.x over the sample's elements; the row index and
+// its four coefficients are block-uniform, read once per sample. The mask holds mask_per values per sample, element j
+// reads mask[n*mask_per + j % mask_per] (a per-pixel mask shared by the channels of NCHW). VEC: 16-byte accesses
+// (per % 4 == 0, mask_per % 4 == 0, every pointer 16-byte aligned): four consecutive elements then sit in one mask
+// period. out may alias x: an element is read before the same thread writes it.
+template <bool VEC>
+__global__ __launch_bounds__(256) void known_blend_kernel(const float* x, const float* x0, const float* mask,
+                                                          int mask_per, const float* z, const float* z2,
+                                                          const int64_t* row, const float* coef, int R, int N, int per,
+                                                          float* out) {
+  for (int n = blockIdx.y; n < N; n += gridDim.y) {
+    long s = row[n];
+    s = s < 0 ? 0 : (s > R - 1 ? R - 1 : s);   // never index past the table
+    const float* c = coef + s * 4;
+    const BlendRow r{c[0], c[1], c[2], c[3]};
+    const bool rz = r.kb != 0.f && z != nullptr, rz2 = r.rb != 0.f && z2 != nullptr;
+    const float noz = r.kb != 0.f ? NAN : 0.f;    // a noised row without its noise buffer: NaN out, no fault
+    const float noz2 = r.rb != 0.f ? NAN : 0.f;
+    const size_t base = (size_t)n * per;
+    const float* mrow = mask + (size_t)n * mask_per;
+    if (VEC) {
+      const int per4 = per / 4;
+      for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < per4; q += gridDim.x * blockDim.x) {
+        const size_t i = base + (size_t)q * 4;
+        const v4f xv = *(const v4f*)(x + i);
+        const v4f x0v = *(const v4f*)(x0 + i);
+        const v4f mv = *(const v4f*)(mrow + (q * 4) % mask_per);
+        v4f zv = {noz, noz, noz, noz}, z2v = {noz2, noz2, noz2, noz2}, ov;
+        if (rz) zv = *(const v4f*)(z + i);
+        if (rz2) z2v = *(const v4f*)(z2 + i);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) ov[k] = blend_elem(r, xv[k], x0v[k], mv[k], zv[k], z2v[k]);
+        *(v4f*)(out + i) = ov;
+      }
+    } else {
+      for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < per; q += gridDim.x * blockDim.x) {
+        const size_t i = base + q;
+        out[i] = blend_elem(r, x[i], x0[i], mrow[q % mask_per], rz ? z[i] : noz, rz2 ? z2[i] : noz2);
+      }
+    }
+  }
+}
+
 // One block per sample: CFG combine, x0 prediction, optional dynamic threshold (torch.quantile, linear).
 __global__ __launch_bounds__(1024) void cfg_x0_kernel(const float* x, const float* ec, const float* eu, float scale,
                                                       const int64_t* t, const float* ta, const float* tb, int mode,
@@ -911,6 +977,23 @@ extern "C" int dmc_dpm_step(const float* x, const float* eps, const float* x0_in
   if (vec) dpm_step_kernel<true><<<grid, 256, 0, s>>>(x, eps, x0_in, x0_prev, step, coef, S, N, per, clip, out, x0_out);
   else dpm_step_kernel<false><<<grid, 256, 0, s>>>(x, eps, x0_in, x0_prev, step, coef, S, N, per, clip, out, x0_out);
   return dmc::check_launch("dmc_dpm_step");
+}
+
+extern "C" int dmc_known_blend(const float* x, const float* x0, const float* mask, int mask_per, const float* z,
+                               const float* z2, const int64_t* row, const float* coef, int R, int N, int per,
+                               float* out, void* stream) {
+  DMC_REQUIRE(R > 0 && N > 0 && per > 0 && mask_per > 0,
+              "known_blend: R %d, N %d, per_sample %d, mask_per %d must be positive", R, N, per, mask_per);
+  DMC_REQUIRE(per % mask_per == 0, "known_blend: mask_per %d does not divide per_sample %d", mask_per, per);
+  DMC_REQUIRE(x && x0 && mask && row && coef && out, "known_blend: only z and z2 may be NULL");
+  const uintptr_t bits = (uintptr_t)x | (uintptr_t)x0 | (uintptr_t)mask | (uintptr_t)z | (uintptr_t)z2 |
+                         (uintptr_t)out;   // a NULL operand adds no bits
+  const bool vec = per % 4 == 0 && mask_per % 4 == 0 && (bits & 15) == 0;
+  const dim3 grid = sample_grid(vec ? per / 4 : per, N, 8192);
+  hipStream_t s = dmc::as_stream(stream);
+  if (vec) known_blend_kernel<true><<<grid, 256, 0, s>>>(x, x0, mask, mask_per, z, z2, row, coef, R, N, per, out);
+  else known_blend_kernel<false><<<grid, 256, 0, s>>>(x, x0, mask, mask_per, z, z2, row, coef, R, N, per, out);
+  return dmc::check_launch("dmc_known_blend");
 }
 
 extern "C" int dmc_cfg_x0(const float* x, const float* ec, const float* eu, float scale, const int64_t* t,

@@ -12,6 +12,8 @@ CFG batches the cond/uncond forwards into one 2B forward and fuses combine + x0 
 (per-row torch.quantile restatement) into dmc_cfg_x0.
 prediction_type='v' (not in the reference; ddpm.py ObjectiveMixin): one dmc_pred_convert launch after the model call
 hands eps and x0 to the same step kernel.
+img2img / inpaint (not in the reference; _edit_loop.EditMixin) run the same steps from, or around, a given image;
+invert runs the eta = 0 step with (t, t_next) swapped, from an image up to its latent.
 """
 import os
 
@@ -20,11 +22,12 @@ from tqdm import tqdm
 
 from .. import kernels as K
 from . import _objective, _schedule
+from ._edit_loop import EditMixin
 from ._graph import StepGraph, cache_for, run_loop
 from .ddpm import ObjectiveMixin, _require_cuda, diffusion_loss, make_betas
 
 
-class DDIM(ObjectiveMixin):
+class DDIM(ObjectiveMixin, EditMixin):
     """DDIM diffusion process with accelerated sampling (diffusion/ddim.py:13-351)."""
 
     def __init__(self, num_timesteps=1000, num_inference_steps=50, beta_start=0.0001, beta_end=0.02,
@@ -107,11 +110,77 @@ class DDIM(ObjectiveMixin):
             return torch.randn_like(x)
         return noise(i) if callable(noise) else noise[i].to(x.device)
 
+    @staticmethod
+    def _shared_t(model, y):
+        """Every sample shares the step's timestep: a model that takes a length-1 t (UNet.shared_timestep) runs its
+        time-embedding MLPs once per step instead of once per image."""
+        return (y is None and getattr(model, "shared_timestep", False)
+                and os.environ.get("DMC_SHARED_T", "1") != "0")   # A/B switch
+
+    def _step_plain(self, model, x, t, tn, y, z, shared_t, clip=True):
+        """One step of sample(): shared with img2img / inpaint / invert."""
+        eps, x0 = (model(x, t[:1], None) if shared_t else None), None
+        if eps is not None and self.prediction_type == "v":
+            eps, x0 = self._convert(eps, x, t)
+        return self.p_sample(model, x, t, tn, y, clip_denoised=clip, eps=eps, x0_pred=x0, noise=z)
+
+    def _step_cfg(self, model, x, t, tn, y, z, cfg_scale, p_threshold):
+        """One step of sample_with_cfg(): shared with img2img / inpaint."""
+        eps_c, eps_u = self._cfg_pair(model, x, t, y)
+        eps_g, x0 = K.cfg_x0(x.contiguous(), eps_c.contiguous(), eps_u.contiguous(), cfg_scale, t,
+                             self._tab("alphas_cumprod", x.device), None, 0, p_threshold)
+        return self.p_sample(model, x, t, tn, y=None, clip_denoised=False, eps=eps_g, x0_pred=x0, noise=z)
+
+    def _edit_steps(self):
+        return len(self.inference_timesteps)
+
+    def _edit_step(self, model, B, dev, y, cfg_scale, p_threshold, i0):
+        """For _edit_loop.EditMixin: (inference timesteps from i0 on, j -> the j-th of those steps' device inputs,
+        step(x, args, y, z), the step draws noise, the graph key's tail)."""
+        tab = self._ts_table(B, dev)[i0:]
+        shared_t = self._shared_t(model, y)
+
+        def step(x, args, yy, z):
+            if cfg_scale is None:
+                return self._step_plain(model, x, args[0], args[1], yy, z, shared_t)
+            return self._step_cfg(model, x, args[0], args[1], yy, z, cfg_scale, p_threshold)
+
+        key = ("ddim", self.prediction_type, self.eta, shared_t, y is not None, cfg_scale, p_threshold,
+               self.alphas_cumprod.data_ptr())
+        return (self.inference_timesteps[i0:].cpu().numpy(), (lambda j: (tab[j], tab[j + 1])), step, self.eta > 0,
+                key)
+
     @torch.no_grad()
-    def sample(self, model, shape, y=None, return_all_timesteps=False, x_T=None, noise=None):
-        """DDIM sampling loop (diffusion/ddim.py:210-249). Optional (not in the reference): x_T, and for eta > 0
-        noise = [S, B, C, H, W] tensor or callable i -> tensor. Steps after the first replay one captured HIP
-        graph (diffusion/_graph.py)."""
+    def invert(self, model, image, y=None, return_all_timesteps=False):
+        """DDIM inversion: the eta = 0 map run backwards, from the image (taken as the state at the smallest
+        inference timestep) up to its latent at the largest: x <- ddim_step(x, eps(x, t_k), t = t_k, t_next = t_k+1)
+        over ascending t_k without clipping, S-1 model evaluations. dmc_ddim_step is symmetric in (t, t_next) at
+        eta = 0, so this is the sampling step with the two swapped."""
+        if self.eta != 0:
+            raise ValueError(f"DDIM inversion needs the deterministic map: eta must be 0, got {self.eta}")
+        x = self._edit_input(image)
+        dev = x.device
+        if y is not None:
+            y = y.to(dev)
+        up = torch.flip(self.inference_timesteps.to(dev), (0,))
+        tab = up.view(-1, 1).expand(-1, x.shape[0]).contiguous()
+        has_y, shared_t = y is not None, self._shared_t(model, y)
+
+        def inputs(k, xx):
+            return (xx, tab[k], tab[k + 1]) + ((y,) if has_y else ())
+
+        def fn(xx, t, tn, yy=None):
+            return self._step_plain(model, xx, t, tn, yy, None, shared_t, clip=False)
+
+        key = ("ddim_invert", self.prediction_type, shared_t, has_y, self.alphas_cumprod.data_ptr())
+        return self._edit_run(model, x, up.shape[0] - 1, inputs, fn, key, (3,) if has_y else (),
+                              return_all_timesteps, "DDIM inversion")
+
+    @torch.no_grad()
+    def sample(self, model, shape, y=None, return_all_timesteps=False, x_T=None, noise=None, clip_denoised=True):
+        """DDIM sampling loop (diffusion/ddim.py:210-249). Optional (not in the reference): x_T, clip_denoised, and
+        for eta > 0 noise = [S, B, C, H, W] tensor or callable i -> tensor. Steps after the first replay one
+        captured HIP graph (diffusion/_graph.py)."""
         batch_size = shape[0]
         device = self.device
         img = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float()
@@ -129,18 +198,13 @@ class DDIM(ObjectiveMixin):
             z = self._noise(noise, i, x)
             return (x, tab[i], tab[i + 1]) + ((y,) if has_y else ()) + ((z,) if z is not None else ())
 
-        # every sample shares the step's timestep: a model that takes a length-1 t (UNet.shared_timestep) runs its
-        # time-embedding MLPs once per step instead of once per image
-        shared_t = (y is None and getattr(model, "shared_timestep", False)
-                    and os.environ.get("DMC_SHARED_T", "1") != "0")   # A/B switch
+        shared_t = self._shared_t(model, y)
+        clip = bool(clip_denoised)
 
         def fn(x, t, tn, *rest):
             yy = rest[0] if has_y else None
             z = rest[-1] if len(rest) > has_y else None
-            eps, x0 = (model(x, t[:1], None) if shared_t else None), None
-            if eps is not None and self.prediction_type == "v":
-                eps, x0 = self._convert(eps, x, t)
-            return self.p_sample(model, x, t, tn, yy, eps=eps, x0_pred=x0, noise=z)
+            return self._step_plain(model, x, t, tn, yy, z, shared_t, clip)
 
         def record(i, x):
             bar.update(1)
@@ -148,7 +212,8 @@ class DDIM(ObjectiveMixin):
                 imgs.append(x.cpu())
 
         cache = None if return_all_timesteps else cache_for(
-            model, ("ddim", self.prediction_type, self.eta, shared_t, has_y, has_z, self.alphas_cumprod.data_ptr()),
+            model, ("ddim", self.prediction_type, self.eta, shared_t, has_y, has_z, clip,
+                    self.alphas_cumprod.data_ptr()),
             self, img)
         img = run_loop(img, S, inputs, fn, StepGraph.eligible(model, img, True, False),
                        record, cache=cache, const=(3,) if has_y else ())
@@ -183,10 +248,7 @@ class DDIM(ObjectiveMixin):
             return (x, tab[i], tab[i + 1], y) + ((z,) if z is not None else ())
 
         def fn(x, t, tn, yy, z=None):
-            eps_c, eps_u = self._cfg_pair(model, x, t, yy)
-            eps_g, x0 = K.cfg_x0(x.contiguous(), eps_c.contiguous(), eps_u.contiguous(), cfg_scale, t, ac, None, 0,
-                                 p_threshold)
-            return self.p_sample(model, x, t, tn, y=None, clip_denoised=False, eps=eps_g, x0_pred=x0, noise=z)
+            return self._step_cfg(model, x, t, tn, yy, z, cfg_scale, p_threshold)
 
         def record(i, x):
             bar.update(1)

@@ -19,14 +19,17 @@ Extra optional keyword arguments (not in the reference, all default to the refer
 p_sample(noise=...), sample(x_T=...), sample_with_cfg(x_T=...) inject the Gaussian draws for parity tests.
 DDPM(prediction_type='v') trains and samples a v-prediction network (arXiv:2202.00512), p_losses(snr_gamma=...)
 weights each sample by min-SNR-gamma (arXiv:2303.09556); see _objective.py. With the defaults neither launches
-anything new.
+anything new. img2img / inpaint (not in the reference either; _edit_loop.EditMixin, _edit.py, dmc_known_blend) run the
+steps of sample / sample_with_cfg from, or around, a given image.
 """
+import numpy as np
 import torch
 import torch.nn.functional as F
 from tqdm import tqdm
 
 from .. import kernels as K
 from . import _objective, _schedule
+from ._edit_loop import EditMixin
 from ._graph import StepGraph, run_loop
 
 
@@ -139,7 +142,7 @@ class ObjectiveMixin:
         return eps[:B], eps[B:]
 
 
-class DDPM(ObjectiveMixin):
+class DDPM(ObjectiveMixin, EditMixin):
     """DDPM diffusion process (diffusion/ddpm.py:15-332)."""
 
     def __init__(self, num_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule='linear', device='cuda',
@@ -226,6 +229,37 @@ class DDPM(ObjectiveMixin):
             return torch.randn_like(x)
         return noise(i) if callable(noise) else noise[i].to(x.device)
 
+    def _step_plain(self, model, x, t, y, z):
+        """One step of sample(): shared with img2img / inpaint."""
+        return self.p_sample(model, x, t, y, noise=z)
+
+    def _step_cfg(self, model, x, t, y, z, cfg_scale, p_threshold):
+        """One step of sample_with_cfg(): shared with img2img / inpaint."""
+        dev = x.device
+        eps_c, eps_u = self._cfg_pair(model, x, t, y)
+        eps_g, x0 = K.cfg_x0(x.contiguous(), eps_c.contiguous(), eps_u.contiguous(), cfg_scale, t,
+                             self._tab("sqrt_recip_alphas_cumprod", dev),
+                             self._tab("sqrt_recipm1_alphas_cumprod", dev), 1, p_threshold)
+        return self.p_sample(model, x, t, y=None, clip_denoised=False, eps=eps_g, x0_pred=x0, noise=z)
+
+    def _edit_steps(self):
+        return self.num_timesteps
+
+    def _edit_step(self, model, B, dev, y, cfg_scale, p_threshold, i0):
+        """For _edit_loop.EditMixin: (timesteps T-1-i0 .. 0, j -> the j-th of those steps' device inputs,
+        step(x, args, y, z), the step draws noise, the graph key's tail)."""
+        T = self.num_timesteps
+        ts = np.arange(T - 1 - i0, -1, -1, dtype=np.int64)
+        tab = torch.from_numpy(ts).to(dev).view(-1, 1).expand(-1, B).contiguous()
+
+        def step(x, args, yy, z):
+            if cfg_scale is None:
+                return self._step_plain(model, x, args[0], yy, z)
+            return self._step_cfg(model, x, args[0], yy, z, cfg_scale, p_threshold)
+
+        key = ("ddpm", self.prediction_type, T, y is not None, cfg_scale, p_threshold, self.alphas_cumprod.data_ptr())
+        return ts, (lambda j: (tab[j],)), step, True, key
+
     @torch.no_grad()
     def sample(self, model, shape, y=None, return_all_timesteps=False, x_T=None, noise=None):
         """Ancestral sampling over all timesteps (diffusion/ddpm.py:222-252). Optional (not in the reference):
@@ -243,7 +277,7 @@ class DDPM(ObjectiveMixin):
             return x, ts[T - 1 - i], self._noise(noise, i, x)
 
         def fn(x, t, z):
-            return self.p_sample(model, x, t, y, noise=z)
+            return self._step_plain(model, x, t, y, z)
 
         def record(i, x):
             bar.update(1)
@@ -285,11 +319,7 @@ class DDPM(ObjectiveMixin):
             return x, ts[T - 1 - i], self._noise(noise, i, x)
 
         def fn(x, t, z):
-            eps_c, eps_u = self._cfg_pair(model, x, t, y)
-            eps_g, x0 = K.cfg_x0(x.contiguous(), eps_c.contiguous(), eps_u.contiguous(), cfg_scale, t,
-                                 self._tab("sqrt_recip_alphas_cumprod", dev),
-                                 self._tab("sqrt_recipm1_alphas_cumprod", dev), 1, p_threshold)
-            return self.p_sample(model, x, t, y=None, clip_denoised=False, eps=eps_g, x0_pred=x0, noise=z)
+            return self._step_cfg(model, x, t, y, z, cfg_scale, p_threshold)
 
         def record(i, x):
             bar.update(1)

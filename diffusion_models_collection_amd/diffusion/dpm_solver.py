@@ -13,8 +13,6 @@ the history, so the same captured step serves every i. CFG reuses dmc_cfg_x0 (gu
 unchanged and hands its x0 to dmc_dpm_step. With prediction_type='v' (ddpm.py ObjectiveMixin) dmc_pred_convert turns
 the model output into that x0 (plain path) or into the two eps halves (CFG) first.
 """
-import os
-
 import torch
 from tqdm import tqdm
 
@@ -48,6 +46,7 @@ class DPMSolver(DDIM):
         coef = _dpm.dpm_coefficients(ac, ts, self.solver_order, self.lower_order_final)
         self.inference_timesteps = torch.from_numpy(ts).to(self.device)
         self.step_coefficients = torch.from_numpy(coef).to(self.device)
+        self.__dict__.pop("_truncated", None)
 
     def p_sample(self, *args, **kwargs):
         raise NotImplementedError("DPMSolver is a multistep solver: a step needs the previous x0 prediction; use "
@@ -89,6 +88,72 @@ class DPMSolver(DDIM):
             return torch.stack(imgs, dim=0)
         return st[0]
 
+    def _step_plain(self, model, st, t, k, y, coef, shared_t, clip=True):
+        """One step of sample(): shared with img2img / inpaint."""
+        x = st[0]
+        eps = model(x, t[:1] if shared_t else t, y)
+        new = torch.empty_like(st)
+        if self.prediction_type == "v":
+            _, x0 = self._convert(eps, x, t)
+            K.dpm_step(x, None, k, coef, clip=clip, x0=x0, x0_prev=st[1], out=new[0], x0_out=new[1])
+        else:
+            K.dpm_step(x, eps.contiguous().float(), k, coef, clip=clip, x0_prev=st[1], out=new[0], x0_out=new[1])
+        return new
+
+    def _step_cfg(self, model, st, t, k, y, coef, cfg_scale, p_threshold):
+        """One step of sample_with_cfg(): shared with img2img / inpaint."""
+        x = st[0]
+        eps_c, eps_u = self._cfg_pair(model, x, t, y)
+        _, x0 = K.cfg_x0(x, eps_c.contiguous(), eps_u.contiguous(), cfg_scale, t,
+                         self._tab("alphas_cumprod", x.device), None, 0, p_threshold)
+        new = torch.empty_like(st)
+        K.dpm_step(x, None, k, coef, clip=False, x0=x0, x0_prev=st[1], out=new[0], x0_out=new[1])
+        return new
+
+    _edit_state = _state
+
+    @staticmethod
+    def _edit_image(st):
+        return st[0]
+
+    def _edit_resample(self, resample):
+        if resample != 1:
+            raise ValueError("DPMSolver.inpaint: resample must be 1 (the multistep history does not survive a "
+                             "re-noise); use DDIM or DDPM to resample")
+
+    def _truncated_coefficients(self, i0, dev):
+        """The coefficient rows for the timesteps from i0 on, rebuilt so that the first executed row is first order
+        (it has no history); built once per i0."""
+        if i0 == 0:
+            return self._tab("step_coefficients", dev)
+        cache = self.__dict__.setdefault("_truncated", {})     # dropped with the timestep list
+        c = cache.get(i0)
+        if c is None or c.device != dev:
+            coef = _dpm.dpm_coefficients(self.alphas_cumprod.cpu().numpy(), self.inference_timesteps[i0:].cpu().numpy(),
+                                         self.solver_order, self.lower_order_final)
+            c = cache[i0] = torch.from_numpy(coef).to(dev)
+        return c
+
+    def _edit_step(self, model, B, dev, y, cfg_scale, p_threshold, i0):
+        """For _edit_loop.EditMixin: (inference timesteps from i0 on, j -> the j-th of those steps' device inputs,
+        step(state, args, y, z), no noise drawn, the graph key's tail)."""
+        tab, idx = self._step_tables(B, dev)
+        tab = tab[i0:]
+        coef = self._truncated_coefficients(i0, dev)
+        shared_t = self._shared_t(model, y)
+
+        def step(st, args, yy, z):
+            if cfg_scale is None:
+                return self._step_plain(model, st, args[0], args[1], yy, coef, shared_t)
+            return self._step_cfg(model, st, args[0], args[1], yy, coef, cfg_scale, p_threshold)
+
+        key = self._key("dpm", coef, shared_t, y is not None, cfg_scale, p_threshold, self.alphas_cumprod.data_ptr())
+        return self.inference_timesteps[i0:].cpu().numpy(), (lambda j: (tab[j], idx[j])), step, False, key
+
+    def invert(self, *args, **kwargs):
+        raise NotImplementedError("DPMSolver has no inversion: the multistep update is not the eta = 0 DDIM map run "
+                                  "backwards; use DDIM.invert")
+
     @torch.no_grad()
     def sample(self, model, shape, y=None, return_all_timesteps=False, x_T=None, clip_denoised=True):
         """S' model evaluations, S' = len(inference_timesteps); the last one returns its x0 prediction."""
@@ -103,23 +168,13 @@ class DPMSolver(DDIM):
             y = y.to(dev)
         has_y = y is not None
         clip = bool(clip_denoised)
-        # as DDIM.sample: a model that takes a length-1 t runs its time-embedding MLPs once per step
-        shared_t = (y is None and getattr(model, "shared_timestep", False)
-                    and os.environ.get("DMC_SHARED_T", "1") != "0")
+        shared_t = self._shared_t(model, y)
 
         def inputs(i, st):
             return (st, tab[i], idx[i]) + ((y,) if has_y else ())
 
         def fn(st, t, k, yy=None):
-            x = st[0]
-            eps = model(x, t[:1] if shared_t else t, yy)
-            new = torch.empty_like(st)
-            if self.prediction_type == "v":
-                _, x0 = self._convert(eps, x, t)
-                K.dpm_step(x, None, k, coef, clip=clip, x0=x0, x0_prev=st[1], out=new[0], x0_out=new[1])
-            else:
-                K.dpm_step(x, eps.contiguous().float(), k, coef, clip=clip, x0_prev=st[1], out=new[0], x0_out=new[1])
-            return new
+            return self._step_plain(model, st, t, k, yy, coef, shared_t, clip)
 
         key = self._key("dpm", coef, clip, shared_t, has_y, self.alphas_cumprod.data_ptr())
         return self._run(model, self._state(img), S, inputs, fn, return_all_timesteps, key,
@@ -148,12 +203,7 @@ class DPMSolver(DDIM):
             return (st, tab[i], idx[i], y)
 
         def fn(st, t, k, yy):
-            x = st[0]
-            eps_c, eps_u = self._cfg_pair(model, x, t, yy)
-            _, x0 = K.cfg_x0(x, eps_c.contiguous(), eps_u.contiguous(), cfg_scale, t, ac, None, 0, p_threshold)
-            new = torch.empty_like(st)
-            K.dpm_step(x, None, k, coef, clip=False, x0=x0, x0_prev=st[1], out=new[0], x0_out=new[1])
-            return new
+            return self._step_cfg(model, st, t, k, yy, coef, cfg_scale, p_threshold)
 
         key = self._key("dpm_cfg", coef, float(cfg_scale), p_threshold, ac.data_ptr())
         return self._run(model, self._state(img), S, inputs, fn, return_all_timesteps, key, (3,),

@@ -765,6 +765,35 @@ def dpm_step(x, eps, step, coef, clip=True, x0=None, x0_prev=None, out=None, x0_
     return out, x0_out
 
 
+def known_blend(x, x0, mask, row, coef, z=None, z2=None, out=None):
+    """Known-region blend (dmc_known_blend): row[n] picks sample n's row {ka, kb, ra, rb} of the [R, 4] table
+    (diffusion/_edit.py); out = ra * (mask * (ka*x0 + kb*z) + (1 - mask) * x) + rb*z2. mask: x's shape, or x's with
+    one channel ([N, 1, ...]: shared by the channels). z / z2 may be None when no row has kb / rb != 0; out may be x."""
+    what = "dmc_known_blend"
+    if out is None:
+        out = torch.empty_like(x)
+    if not x.is_cuda or x.dim() < 1 or x.numel() < 1:
+        raise L.DMCError(f"{what}: x must be a non-empty device tensor, got {tuple(x.shape)} on {x.device}")
+    N = x.shape[0]
+    per = x.numel() // N
+    _same(x, x0, z, z2, out, what=what)
+    if row is None:
+        raise L.DMCError(f"{what}: needs a row index")
+    _steps(N, x.device, row, what=what)
+    shared = x.dim() >= 2 and tuple(mask.shape) == (N, 1) + tuple(x.shape[2:])
+    if mask.device != x.device or not (mask.shape == x.shape or shared):
+        raise L.DMCError(f"{what}: mask {tuple(mask.shape)} on {mask.device} is neither {tuple(x.shape)} nor that "
+                         f"with one channel on {x.device}")
+    _fp32_contig(what, x, x0, mask, z, z2, out)
+    if (coef.dim() != 2 or coef.shape[1] != 4 or coef.shape[0] < 1 or coef.dtype != torch.float32
+            or coef.device != x.device or not coef.is_contiguous()):
+        raise L.DMCError(f"{what}: coef must be a contiguous fp32 [R, 4] tensor on {x.device}, got "
+                         f"{coef.dtype} {tuple(coef.shape)} on {coef.device}")
+    check(LIB.dmc_known_blend(ptr(x), ptr(x0), ptr(mask), mask.numel() // N, ptr(z), ptr(z2), ptr(row), ptr(coef),
+                              coef.shape[0], N, per, ptr(out), L.stream()), what)
+    return out
+
+
 def cfg_x0(x, ec, eu, scale, t, ta, tb, mode, p_threshold, out=None):
     """(eps, x0) of the guided step; out: the two buffers to fill (allocated if None)."""
     N = x.shape[0]

@@ -407,6 +407,22 @@ int dmc_ddpm_step(const float* x, const float* eps, const float* x0_in, const in
 int dmc_dpm_step(const float* x, const float* eps, const float* x0_in, const float* x0_prev,
                  const int64_t* step, const float* coef, int S, int N, int per_sample, int clip,
                  float* out, float* x0_out, void* stream);
+/* Known-region blend of the editing samplers (not in the reference): inpainting as RePaint (Lugmayr et
+ * al. 2022, arXiv:2201.09865) and SDEdit's image-to-image (Meng et al. 2021, arXiv:2108.01073).
+ * coef: [R][4] fp32 rows {ka, kb, ra, rb} (diffusion/_edit.py); row[n] in [0,R) picks sample n's row (an
+ * index outside is clamped into the table). mask: [N][mask_per], mask_per == per_sample or a divisor of it
+ * (a per-pixel mask shared by the channels of NCHW); element j of sample n reads
+ * m = mask[n*mask_per + j % mask_per], 1 keeps the given image x0.
+ *   known = kb != 0 ? ka*x0[i] + kb*z[i] : ka*x0[i]     -- x0 noised to the step's target level
+ *   b     = m*known + (1 - m)*x[i]
+ *   out   = rb != 0 ? ra*b + rb*z2[i] : b               -- the forward jump of a resampling repetition
+ * Each op rounded once, no fma. A row with kb == 0 never reads z, one with rb == 0 never reads z2 (either
+ * may be NULL or hold NaN); a row with kb != 0 and z == NULL, or rb != 0 and z2 == NULL, gives NaN. out may
+ * be the same buffer as x. 16-byte accesses when per_sample % 4 == 0, mask_per % 4 == 0 and every pointer
+ * read or written is 16-byte aligned, element-wise otherwise. */
+int dmc_known_blend(const float* x, const float* x0, const float* mask, int mask_per, const float* z,
+                    const float* z2, const int64_t* row, const float* coef, int R, int N, int per_sample,
+                    float* out, void* stream);
 /* CFG + x0 prediction + dynamic threshold (diffusion/ddim.py:300-325, ddpm.py:284-303):
  * eps = eu + s*(ec - eu) -> eps_out; x0 = mode 0: (x - sqrt(1-a)eps)/sqrt(a) [DDIM]
  * mode 1: sra*x - srm1*eps [DDPM]; threshold: p in (0,1): per-row quantile of |x0| (linear
