@@ -19,7 +19,9 @@ PRO_NONE, PRO_AFFINE_SILU, PRO_SILU, PRO_AFFINE, PRO_GN_SILU = 0, 1, 2, 3, 4
 LOSS = {"l1": 0, "l2": 1, "huber": 2}
 PRED = {"eps": 0, "v": 1}    # include/dmc.h DMC_PRED_*
 OBJECTIVE_MAX_BLOCKS = 64    # include/dmc.h DMC_OBJECTIVE_MAX_BLOCKS
-PACK_FWD, PACK_DGRAD, PACK_UPDGRAD = 0, 1, 2
+PACK_FWD, PACK_DGRAD, PACK_UPDGRAD, PACK_UPFOLD, PACK_DOWNDGRAD = 0, 1, 2, 3, 4
+FOLD_NONE, FOLD_UP, FOLD_DOWN_DGRAD = 0, 1, 2   # include/dmc.h DMC_FOLD_*
+FOLD_PACK = {FOLD_UP: PACK_UPFOLD, FOLD_DOWN_DGRAD: PACK_DOWNDGRAD}
 
 _c_int, _c_p, _c_f, _c_u32, _c_long, _c_size = (ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_uint32,
                                                 ctypes.c_long, ctypes.c_size_t)
@@ -42,6 +44,7 @@ class ConvDesc(ctypes.Structure):
         ("silu_pre", _c_p), ("ld_silu", _c_int), ("Csplit", _c_int), ("ldy1", _c_int), ("ldy2", _c_int),
         ("out_f32", _c_int), ("out_nchw", _c_int), ("act", _c_int), ("y_pre", _c_p), ("ld_pre", _c_int),
         ("gn_part", _c_p), ("wg_bias", _c_p), ("pro_groups", _c_int), ("pro_eps", _c_f),
+        ("fold", _c_int),
     ]
 
 
@@ -114,6 +117,7 @@ def _load():
         "dmc_conv2d_workspace": (_c_size, [ctypes.POINTER(ConvDesc)]),
         "dmc_conv_halo_prologue": (_c_int, [ctypes.POINTER(ConvDesc)]),
         "dmc_conv2d_fused_epilogue": (_c_int, [ctypes.POINTER(ConvDesc), ctypes.c_size_t]),
+        "dmc_conv_resample_fold": (_c_int, [ctypes.POINTER(ConvDesc), ctypes.c_size_t]),
         "dmc_conv2d_plan": (_c_int, [ctypes.POINTER(ConvDesc), ctypes.c_size_t, ctypes.POINTER(ConvPlan)]),
         "dmc_conv2d": (_c_int, [ctypes.POINTER(ConvDesc), _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_size, _c_p]),
         "dmc_conv2d_wgrad_workspace": (_c_size, [ctypes.POINTER(ConvDesc)]),

@@ -275,8 +275,10 @@ DMC_DEV void chan_eq(float& m, float& q, float mb, float qb, float n) {
   m = 0.5f * (m + mb);
 }
 
-template <int BM, int BN, int NT>
-DMC_DEV void tile_epilogue8(const ConvK& a, const char* lds, int EP, int m0, int n0) {
+// CLS: the block is one output-parity class of a folded resampling conv (ConvK::cls): pixels and GroupNorm segments
+// are the class grid's and go through cls_out_pixel / cls_out_seg where they address memory.
+template <int BM, int BN, int NT, bool CLS = false>
+DMC_DEV void tile_epilogue8(const ConvK& a, const char* lds, int EP, int m0, int n0, int par = 0) {
   constexpr int CG = BN / 8, RS = NT / CG, IT = BM / RS;
   constexpr int SEG = 64, NSEG = BM / SEG, KPS = SEG / RS;   // GroupNorm partial segments of 64 pixels
   static_assert((CG == 16 || CG == 8) && SEG % RS == 0 && BM % SEG == 0, "GroupNorm partial geometry");
@@ -299,7 +301,8 @@ DMC_DEV void tile_epilogue8(const ConvK& a, const char* lds, int EP, int m0, int
 #pragma unroll
     for (int k = 0; k < IT; ++k) {
       const int pix = min(m0 + r0 + k * RS, a.M - 1);
-      rr[k] = *(const v4i*)(a.resid + ((size_t)pix * a.ld_res + co) * 2);
+      const int po = CLS ? cls_out_pixel(a, par, pix) : pix;
+      rr[k] = *(const v4i*)(a.resid + ((size_t)po * a.ld_res + co) * 2);
     }
   }
   int n = (m0 + r0) / a.OHW, nend = (n + 1) * a.OHW;
@@ -353,7 +356,8 @@ DMC_DEV void tile_epilogue8(const ConvK& a, const char* lds, int EP, int m0, int
         }
       }
       const v4i out = Chunk<bf16_t>::pack(f);
-      *(v4i*)(y + ((size_t)pix * ldy + cy) * 2) = out;
+      const int po = CLS ? cls_out_pixel(a, par, pix) : pix;
+      *(v4i*)(y + ((size_t)po * ldy + cy) * 2) = out;
       if (a.gst) {
         float g[8];
         Chunk<bf16_t>::unpack(out, g);
@@ -410,7 +414,8 @@ DMC_DEV void tile_epilogue8(const ConvK& a, const char* lds, int EP, int m0, int
         m += d * (nb / (na + nb));
         q += qb + d * d * (na * nb / (na + nb));
       }
-      const size_t o = ((size_t)(m0 / SEG + j) * (a.Cout / 8) + (n0 / 8 + c)) * 2;
+      const int seg = CLS ? cls_out_seg(a, par, m0 / SEG + j) : m0 / SEG + j;
+      const size_t o = ((size_t)seg * (a.Cout / 8) + (n0 / 8 + c)) * 2;
       a.gst[o] = m;
       a.gst[o + 1] = q;
     }
@@ -423,8 +428,12 @@ DMC_DEV void tile_epilogue8(const ConvK& a, const char* lds, int EP, int m0, int
 // and the image index is tracked incrementally instead of divided per element (conv_store_tile's general
 // form costs more VALU than the tile's MFMAs leave room for). NCHW output, fused silu' and ragged channel
 // groups take conv_store_tile.
-template <typename T, int BM, int BN, int NT>
-DMC_DEV void tile_epilogue(const ConvK& a, const char* lds, int EP, int m0, int n0) {
+template <typename T, int BM, int BN, int NT, bool CLS = false>
+DMC_DEV void tile_epilogue(const ConvK& a, const char* lds, int EP, int m0, int n0, int par = 0) {
+  if constexpr (CLS) {   // a folded resampling conv is planned only where the 16-byte form applies (fold_kind)
+    tile_epilogue8<BM, BN, NT, true>(a, lds, EP, m0, n0, par);
+    return;
+  }
   constexpr int CG = BN / 4, RS = NT / CG;
   const int cg = threadIdx.x % CG, r0 = threadIdx.x / CG;
   const int co = n0 + cg * 4;
@@ -555,7 +564,8 @@ __host__ __device__ inline bool reg_epi_ok(const ConvK& a) {
          a.act == DMC_ACT_NONE && (a.Cout & 127) == 0 && (a.ldy1 & 7) == 0 &&
          (!a.resid || (a.ld_res & 7) == 0) && (a.M & 127) == 0 && (!a.gst || a.OHW % 64 == 0);
 }
-DMC_DEV void reg_epilogue(const ConvK& a, v4f (&acc)[4][4], int m0, int n0, int wm, int wn) {
+template <bool CLS = false>
+DMC_DEV void reg_epilogue(const ConvK& a, v4f (&acc)[4][4], int m0, int n0, int wm, int wn, int par = 0) {
   // Stores and residual loads are 16 bytes: the lane pair (fh, fh ^ 1) holds the two 4-channel halves of one
   // 8-channel chunk, so for each pair of pixel fragments (j0, j1) one xor-16 exchange of 2 dwords gives the even
   // lane the whole chunk of pixel j0 and the odd lane that of pixel j1 (8-byte stores are store-issue bound).
@@ -575,7 +585,8 @@ DMC_DEV void reg_epilogue(const ConvK& a, v4f (&acc)[4][4], int m0, int n0, int 
     for (int jp = 0; jp < 2; ++jp) {
       rra[i][jp] = v4i{0, 0, 0, 0};
       if (a.resid) {   // 16 bytes of the chunk: pixel j0 (even lane) or j1 (odd lane)
-        const int px = m0 + wm * 64 + (2 * jp + (odd ? 1 : 0)) * 16 + fr;
+        const int pc = m0 + wm * 64 + (2 * jp + (odd ? 1 : 0)) * 16 + fr;
+        const int px = CLS ? cls_out_pixel(a, par, pc) : pc;
         rra[i][jp] = *(const v4i*)(a.resid + ((size_t)px * a.ld_res + cc) * 2);
       }
     }
@@ -639,7 +650,8 @@ DMC_DEV void reg_epilogue(const ConvK& a, v4f (&acc)[4][4], int m0, int n0, int 
       v4i outv;
       if (!odd) { outv[0] = o[0][0]; outv[1] = o[0][1]; outv[2] = recv[0]; outv[3] = recv[1]; }
       else { outv[0] = recv[0]; outv[1] = recv[1]; outv[2] = o[1][0]; outv[3] = o[1][1]; }
-      const int pxs = m0 + wm * 64 + (2 * jp + (odd ? 1 : 0)) * 16 + fr;
+      const int pcs = m0 + wm * 64 + (2 * jp + (odd ? 1 : 0)) * 16 + fr;
+      const int pxs = CLS ? cls_out_pixel(a, par, pcs) : pcs;
       *(v4i*)(a.y1 + ((size_t)pxs * a.ldy1 + cc) * 2) = outv;
     }
     if (a.gst) {
@@ -651,7 +663,8 @@ DMC_DEV void reg_epilogue(const ConvK& a, v4f (&acc)[4][4], int m0, int n0, int 
         cnt *= 2.f;
       }
       if (fr == 0 && !odd) {
-        const size_t o = ((size_t)((m0 + wm * 64) / 64) * (a.Cout / 8) + cc / 8) * 2;
+        const int seg = CLS ? cls_out_seg(a, par, (m0 + wm * 64) / 64) : (m0 + wm * 64) / 64;
+        const size_t o = ((size_t)seg * (a.Cout / 8) + cc / 8) * 2;
         a.gst[o] = gm;
         a.gst[o + 1] = gq;
       }
@@ -665,9 +678,14 @@ DMC_DEV void reg_epilogue(const ConvK& a, v4f (&acc)[4][4], int m0, int n0, int 
 // BUF = false: generic (any channel split) with flat global_load_lds and a zero page.
 // STAGES = LDS ring depth: 3 (one block per CU for the 256x128 tile), or 2 for the 128x128 tile so that two
 // blocks share a CU (one's prologue / epilogue overlaps the other's K loop).
-template <int WM, int WN, bool BUF, int STAGES = 3>
+// CLS = true: a folded resampling conv (ConvK::cls, no split-K): grid.z walks the four output-parity classes, longest
+// K loop first; the block takes its class's tap grid and weights, its K loop is ntaps(class) * Kc / 64 stages, and
+// the epilogue stores to the class's pixels of the high-resolution output.
+template <int WM, int WN, bool BUF, int STAGES = 3, bool CLS = false>
 __global__ __launch_bounds__(WM * WN * 64) void conv_fwd_glds_kernel(ConvK a) {
   using T = bf16_t;
+  const int par = CLS ? 3 - (int)blockIdx.z : 0;
+  const ConvCls cq = CLS ? cls_select(a, par) : ConvCls{a.ntaps, a.tkw, a.tdy0, a.tdx0, a.tsy, a.tsx, 0};
   constexpr int NW = WM * WN;
   constexpr int BM = 64 * WM, BN = 64 * WN;
   constexpr int SB = (BM + BN) * 128;           // bytes per stage
@@ -683,7 +701,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_fwd_glds_kernel(ConvK a) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wave % WM, wn = wave / WM;
   int mb = blockIdx.x, nb = blockIdx.y;
-  if (!a.sk && gridDim.y == 1) xcd_tile((a.Cout + BN - 1) / BN, mb, nb);   // 1-D grid: XCD-aware tile order
+  if ((CLS || !a.sk) && gridDim.y == 1) xcd_tile((a.Cout + BN - 1) / BN, mb, nb);   // 1-D grid: XCD-aware tile order
   const int m0 = mb * BM;
   const int n0 = nb * BN;
   const int lrow = lane >> 3;
@@ -702,7 +720,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_fwd_glds_kernel(ConvK a) {
       pn[j] = -1; poy[j] = 0; pox[j] = 0;
     }
   }
-  const int nstages = a.ntaps * (a.Kc / 64);
+  const int nstages = cq.ntaps * (a.Kc / 64);
 
   v4f acc[4][4];
 #pragma unroll
@@ -711,8 +729,8 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_fwd_glds_kernel(ConvK a) {
     for (int j = 0; j < 4; ++j) acc[i][j] = v4f{0.f, 0.f, 0.f, 0.f};
 
   // split-K (grid.z): this block accumulates stages [s_begin, s_end) and writes fp32 partials
-  const int s_begin = a.sk ? blockIdx.z * a.sk_per : 0;
-  const int s_end = a.sk ? min(nstages, s_begin + a.sk_per) : nstages;
+  const int s_begin = (!CLS && a.sk) ? blockIdx.z * a.sk_per : 0;   // CLS: blockIdx.z is the class, never a split
+  const int s_end = (!CLS && a.sk) ? min(nstages, s_begin + a.sk_per) : nstages;
   const int ns = s_end - s_begin;
   // stages are issued in order, so the tap / channel offset advance incrementally and the per-row
   // source pixels are recomputed only when the tap changes (once per Kc/64 stages)
@@ -721,17 +739,18 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_fwd_glds_kernel(ConvK a) {
   int sp[AI];
   unsigned o1[AI], o2[AI], ob[BI];
   if constexpr (BUF) {
-    const unsigned wrow = (unsigned)(a.ntaps * a.Kc);
+    const unsigned wrow = (unsigned)(cq.ntaps * a.Kc);
 #pragma unroll
     for (int j = 0; j < BI; ++j) {
       const int co = n0 + (wave * BI + j) * 8 + lrow;
-      ob[j] = co < a.Cout ? ((unsigned)co * wrow + lc * 8) * 2u : kOOB;
+      ob[j] = co < a.Cout ? (unsigned)cq.woff + ((unsigned)co * wrow + lc * 8) * 2u : kOOB;
     }
   }
   auto tap_rows = [&]() {
 #pragma unroll
     for (int j = 0; j < AI; ++j) {
-      const int p = pn[j] >= 0 ? src_pixel(a, pn[j], poy[j], pox[j], is_tap) : -1;
+      const int p = pn[j] < 0 ? -1 : CLS ? cls_src_pixel(a, cq, pn[j], poy[j], pox[j], is_tap)
+                                        : src_pixel(a, pn[j], poy[j], pox[j], is_tap);
       if constexpr (BUF) {
         o1[j] = p >= 0 ? ((unsigned)p * a.ld1 + lc * 8) * 2u : kOOB;
         o2[j] = p >= 0 ? ((unsigned)p * a.ld2 + lc * 8) * 2u : kOOB;
@@ -749,7 +768,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_fwd_glds_kernel(ConvK a) {
       glds_issue<AI, BI, BM>(a, base, (s_begin + S) * 64, is_c0, wave, lrow, lc, n0, sp);
     }
     is_c0 += 64;
-    if (is_c0 == a.Kc) { is_c0 = 0; ++is_tap; if (is_tap < a.ntaps) tap_rows(); }
+    if (is_c0 == a.Kc) { is_c0 = 0; ++is_tap; if (is_tap < cq.ntaps) tap_rows(); }
   };
 #define DMC_GLDS_ISSUE(S) issue(S)
   for (int q = 0; q < STAGES - 1 && q < ns; ++q) DMC_GLDS_ISSUE(q);
@@ -805,8 +824,8 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_fwd_glds_kernel(ConvK a) {
   // keeps hipcc from spilling the accumulators to scratch).
   constexpr int EP = BN * 4 + 16;
   if constexpr (WM == 2 && WN == 2) {
-    if (!a.sk && reg_epi_ok(a) && n0 + BN <= a.Cout && m0 + BM <= a.M) {
-      reg_epilogue(a, acc, m0, n0, wm, wn);
+    if ((CLS || !a.sk) && reg_epi_ok(a) && n0 + BN <= a.Cout && m0 + BM <= a.M) {
+      reg_epilogue<CLS>(a, acc, m0, n0, wm, wn, par);
       return;
     }
   }
@@ -817,7 +836,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_fwd_glds_kernel(ConvK a) {
     for (int i = 0; i < 4; ++i)
       *(v4f*)(lds + (wm * 64 + j * 16 + fr) * EP + (wn * 64 + i * 16 + fh * 4) * 4) = acc[i][j];
   __syncthreads();
-  if (a.sk) {
+  if (!CLS && a.sk) {
     // raw partial sums -> slab [z][M][Cpad]
     const int Cpad = gridDim.y * BN;
     float* slab = a.sk + (size_t)blockIdx.z * a.M * Cpad;
@@ -827,7 +846,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_fwd_glds_kernel(ConvK a) {
     }
     return;
   }
-  tile_epilogue<T, BM, BN, NW * 64>(a, lds, EP, m0, n0);
+  tile_epilogue<T, BM, BN, NW * 64, CLS>(a, lds, EP, m0, n0, par);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1554,6 +1573,48 @@ bool dma_operands_ok(const ConvK& k) {
          k.w_bytes > 0;
 }
 
+// Which output-parity fold (DMC_FOLD_*, include/dmc.h dmc_conv_resample_fold) the conv has the form of, 0 for none:
+// bf16 through buffer resources, the nearest-x2 forward (9 forward taps, mode UPSAMPLE) or the stride-2 input gradient
+// (9 flipped taps, mode DILATE) onto an output of exactly twice the source size, and one bf16 NHWC output with 8-channel
+// alignment, so that only the 16-byte epilogues (tile_epilogue8 / reg_epilogue), which know the class store, run.
+int fold_kind(const ConvK& k) {
+  if (k.dtype_bytes != 2 || k.prologue != DMC_PRO_NONE || !dma_operands_ok(k)) return DMC_FOLD_NONE;
+  if (k.ntaps != 9 || k.tkw != 3 || k.stride != 1 || k.OH != 2 * k.H || k.OW != 2 * k.W) return DMC_FOLD_NONE;
+  if (k.out_f32 || k.out_nchw || k.silu_pre || k.addvec || k.act != DMC_ACT_NONE || k.Csplit != k.Cout ||
+      ((k.Cout | k.ldy1 | k.ld_res) & 7) || (long)k.N * k.OH * k.OW >= (1l << 31))
+    return DMC_FOLD_NONE;
+  if (k.mode == DMC_MODE_UPSAMPLE && k.tdy0 == -1 && k.tsy == 1 && k.tdx0 == -1 && k.tsx == 1)
+    // 16 folded taps must fit the weights' buffer resource; whole 64-pixel GroupNorm segments per class and image
+    return ((long)k.Cout * 16 * k.Kc * 2 < 0x7fff0000l && (k.H * k.W) % 64 == 0) ? DMC_FOLD_UP : DMC_FOLD_NONE;
+  if (k.mode == DMC_MODE_DILATE && k.tdy0 == 1 && k.tsy == -1 && k.tdx0 == 1 && k.tsx == -1) return DMC_FOLD_DOWN_DGRAD;
+  return DMC_FOLD_NONE;
+}
+
+// Rewrites k (a conv with fold_kind(k) == kind) as its four parity classes over the low-resolution grid.
+// UP, class (a, b): low-resolution rows i + a - 1 and i + a, columns j + b - 1 and j + b (a 2x2 grid, step +1).
+// DOWN_DGRAD, class (a, b): parity 0 keeps the centre tap (dy row i), parity 1 the taps ky = 0 (row i + 1) and ky = 2
+// (row i): origin +parity, step -1, the original ky-major order, so the fp32 accumulation sequence is the dilated
+// form's without its zero stages.
+void set_fold(ConvK& k, int kind) {
+  int base = 0;   // taps packed before the class
+  for (int c = 0; c < 4; ++c) {
+    ConvCls q{};
+    const int a = c >> 1, b = c & 1;
+    if (kind == DMC_FOLD_UP) {
+      q.ntaps = 4; q.tkw = 2; q.tdy0 = a - 1; q.tdx0 = b - 1; q.tsy = 1; q.tsx = 1;
+    } else {
+      q.tkw = b ? 2 : 1; q.ntaps = (a ? 2 : 1) * q.tkw; q.tdy0 = a; q.tdx0 = b; q.tsy = -1; q.tsx = -1;
+    }
+    k.cls[c] = cls_pack(q, base);
+    base += q.ntaps;
+  }
+  k.w_bytes = base * k.Cout * k.Kc * 2;
+  k.ncls = 4;
+  k.mode = DMC_MODE_NORMAL;
+  k.OH = k.H; k.OW = k.W; k.OHW = k.H * k.W; k.M = k.N * k.OHW;
+  k.ntaps = 4;   // the longest class (the kernel takes each class's own count)
+}
+
 // The whole-image small-map kernel applies (bf16 3x3 stride 1 on 4x4 / 8x8 maps, 64-aligned sources, no prologue,
 // DMC_IMG_MASK bit set for the shape: bit 0 4x4 forward, 1 4x4 input gradient, 2 8x8 forward, 3 8x8 input
 // gradient; default 15): returns its channel tile BN (16 or 32), or 0. Same-box A/B of the B = 128 bench
@@ -2011,10 +2072,35 @@ void launch_splitk_epi_gn(const ConvK& k, int splits, int Cpad, hipStream_t s) {
 // Value of packed element (row, tap t, column k) of an fp32 master weight [Cout][Cin][kh][kw].
 // FWD: dst[co][t][c]; DGRAD: dst[c][t][co]; UPDGRAD: dst[c][u*4+v][co] (nearest-x2 upsample folded into a
 // 4x4 stride-2 kernel). Columns past the source extent are the zero padding of Kc.
+// The two class-ordered packs of the folded resampling convs take t = class * 4 + tap, class = a * 2 + b (the output
+// parity): UPFOLD dst[class][co][r*2+c][c'] = the fp32 sum, in ascending 3x3 tap order, of the taps (ky, kx) that read
+// low-resolution offset (a - 1 + r, b - 1 + c) after a nearest-x2 upsample: floor((a + ky - 1) / 2) = a - 1 + r;
+// DOWNDGRAD dst[class][c][tap][co] = the class's taps of the stride-2 input gradient, ky-major: parity 0 keeps the
+// centre tap, parity 1 the taps 0 and 2.
+DMC_DEV int fold_lo(int par, int r) { return r == 0 ? 0 : par ? 2 : 1; }
+DMC_DEV int fold_hi(int par, int r) { return r == 0 ? (par ? 1 : 0) : 2; }
+// weights w9[ky*3+kx] of one (co, c) folded for class (a, b), tap (r, c)
+DMC_DEV float fold_sum(const float* w9, int a, int b, int r, int c) {
+  float v = 0.f;
+  for (int ky = fold_lo(a, r); ky <= fold_hi(a, r); ++ky)
+    for (int kx = fold_lo(b, c); kx <= fold_hi(b, c); ++kx) v += w9[ky * 3 + kx];
+  return v;
+}
+// class a*2+b of the stride-2 input gradient: taps, and the base of its block in units of (rows x Kc)
+DMC_DEV int down_ntaps(int cls) { return cls == 0 ? 1 : cls == 3 ? 4 : 2; }
+DMC_DEV int down_base(int cls) { return cls == 0 ? 0 : cls == 1 ? 1 : cls == 2 ? 3 : 5; }
+
 DMC_DEV float pack_value(int mode, const float* w, int Cout, int Cin, int kh, int kw, int row, int t, int k) {
   if (mode == DMC_PACK_FWD) return k < Cin ? w[((size_t)row * Cin + k) * kh * kw + t] : 0.f;
+  if (mode == DMC_PACK_UPFOLD)
+    return k < Cin ? fold_sum(w + ((size_t)row * Cin + k) * 9, t >> 3, (t >> 2) & 1, (t >> 1) & 1, t & 1) : 0.f;
   if (k >= Cout) return 0.f;
   if (mode == DMC_PACK_DGRAD) return w[((size_t)k * Cin + row) * kh * kw + t];
+  if (mode == DMC_PACK_DOWNDGRAD) {
+    const int a = t >> 3, b = (t >> 2) & 1, tt = t & 3, ntx = b ? 2 : 1;
+    const int ky = a ? 2 * (tt / ntx) : 1, kx = b ? 2 * (tt % ntx) : 1;
+    return w[((size_t)k * Cin + row) * 9 + ky * 3 + kx];
+  }
   // folded taps: offset u in {-1,0,1,2} <- set of kh with (dj + 1 - kh == u), dj in {0,1}
   const int u = t >> 2, vv = t & 3;  // u,v index 0..3 <-> offset -1..2
   const int khs[4][2] = {{2, -1}, {1, 2}, {0, 1}, {0, -1}};
@@ -2034,13 +2120,23 @@ DMC_DEV float pack_value(int mode, const float* w, int Cout, int Cin, int kh, in
 
 template <typename T>
 __global__ void pack_weight_kernel(int mode, const float* w, int Cout, int Cin, int kh, int kw, int Kc, T* dst) {
-  const int ntaps = (mode == DMC_PACK_UPDGRAD) ? 16 : kh * kw;
-  const int rows = (mode == DMC_PACK_FWD) ? Cout : Cin;
+  const int ntaps = (mode == DMC_PACK_UPDGRAD || mode == DMC_PACK_UPFOLD) ? 16 : kh * kw;
+  const int rows = (mode == DMC_PACK_FWD || mode == DMC_PACK_UPFOLD) ? Cout : Cin;
   const long total = (long)rows * ntaps * Kc;
   for (long o = blockIdx.x * (long)blockDim.x + threadIdx.x; o < total; o += (long)gridDim.x * blockDim.x) {
     const int k = o % Kc;
     const long r = o / Kc;
-    const float v = pack_value(mode, w, Cout, Cin, kh, kw, r / ntaps, r % ntaps, k);
+    float v;
+    if (mode == DMC_PACK_UPFOLD) {          // [class][co][4 taps]
+      const int cls = (int)(r / (4l * rows));
+      v = pack_value(mode, w, Cout, Cin, kh, kw, (int)(r / 4 % rows), cls * 4 + (int)(r % 4), k);
+    } else if (mode == DMC_PACK_DOWNDGRAD) {   // [class][c][1, 2, 2, 4 taps]
+      const int cls = r < rows ? 0 : r < 3l * rows ? 1 : r < 5l * rows ? 2 : 3;
+      const int nt = down_ntaps(cls), r2 = (int)(r - (long)down_base(cls) * rows);
+      v = pack_value(mode, w, Cout, Cin, kh, kw, r2 / nt, cls * 4 + r2 % nt, k);
+    } else {
+      v = pack_value(mode, w, Cout, Cin, kh, kw, r / ntaps, r % ntaps, k);
+    }
     if (sizeof(T) == 4) ((float*)dst)[o] = v;
     else ((bf16_t*)dst)[o] = (bf16_t)f2bf(v);
   }
@@ -2072,7 +2168,7 @@ __global__ __launch_bounds__(256) void pack_tiles_kernel(const dmc_pack_job* job
     if (f32) ((float*)J.dst)[di] = v;
     else ((bf16_t*)J.dst)[di] = (bf16_t)f2bf(v);
   };
-  if (J.mode == DMC_PACK_FWD) {
+  if (J.mode == DMC_PACK_FWD || J.mode == DMC_PACK_UPFOLD) {
     // tile = (rows co0..co0+3, 256 columns k0..): row r's run w[co0+r][k0..k0+kv)[taps] lands at sw[r*256*9..]
     const int co0 = tl[1], k0 = tl[2];
     const int nco = min(kPackFwdCo, J.Cout - co0);
@@ -2098,6 +2194,15 @@ __global__ __launch_bounds__(256) void pack_tiles_kernel(const dmc_pack_job* job
           if (r < nco && tid + u * 256 < run) sw[r * kPackFwdK * 9 + tid + u * 256] = v[r][u];
     }
     __syncthreads();
+    if (J.mode == DMC_PACK_UPFOLD) {   // 16 (class, tap) rows per output channel, each the folded sum of pack_value
+      for (int r = 0; r < nco; ++r)
+        for (int ct = 0; ct < 16; ++ct)
+          for (int k = tid; k < kn; k += 256) {
+            const float v = k < kv ? fold_sum(sw + r * kPackFwdK * 9 + k * 9, ct >> 3, (ct >> 2) & 1, (ct >> 1) & 1, ct & 1) : 0.f;
+            store((((long)(ct >> 2) * J.Cout + co0 + r) * 4 + (ct & 3)) * J.Kc + koff + k0 + k, v);
+          }
+      return;
+    }
     if (!f32 && ((J.Kc | koff | k0 | kn) & 1) == 0) {   // bf16 pairs: one 4-byte store per two columns (round 6)
       for (int r = 0; r < nco; ++r)
         for (int t = 0; t < khkw; ++t)
@@ -2140,11 +2245,17 @@ __global__ __launch_bounds__(256) void pack_tiles_kernel(const dmc_pack_job* job
   }
   __syncthreads();
   const int ntaps = J.mode == DMC_PACK_UPDGRAD ? 16 : khkw;
+  // packed row of (input channel c, tap t); DOWNDGRAD: tap t = (ky, kx) belongs to class (ky != 1, kx != 1)
+  auto drow = [&](int c, int t) -> long {
+    if (J.mode != DMC_PACK_DOWNDGRAD) return (long)c * ntaps + t;
+    const int ky = t / 3, kx = t - ky * 3, a = ky != 1, b = kx != 1, ntx = b ? 2 : 1, cls = a * 2 + b;
+    return (long)down_base(cls) * J.Cin + (long)c * down_ntaps(cls) + (ky >> 1) * ntx + (kx >> 1);
+  };
   auto value = [&](int co, int c, int t) {   // packed value of column co (output channel co0 + co), row (c, t)
     float v = 0.f;
     if (co < cov) {
       const float* wp = sw + co * kPackDgP + c * khkw;
-      if (J.mode == DMC_PACK_DGRAD) {
+      if (J.mode == DMC_PACK_DGRAD || J.mode == DMC_PACK_DOWNDGRAD) {
         v = wp[t];
       } else {
         // folded nearest-x2 taps (see pack_value)
@@ -2168,7 +2279,7 @@ __global__ __launch_bounds__(256) void pack_tiles_kernel(const dmc_pack_job* job
     for (int q = 2 * wv + (ln >> 5); q < cn * ntaps; q += 8) {
       const int c = q / ntaps, t = q - c * ntaps;
       if (cp >= con) continue;
-      *(uint32_t*)((bf16_t*)J.dst + ((long)(c0 + c) * ntaps + t) * J.Kc + koff + co0 + cp) =
+      *(uint32_t*)((bf16_t*)J.dst + drow(c0 + c, t) * J.Kc + koff + co0 + cp) =
           f2bf2(value(cp, c, t), value(cp + 1, c, t));
     }
     return;
@@ -2177,7 +2288,7 @@ __global__ __launch_bounds__(256) void pack_tiles_kernel(const dmc_pack_job* job
   for (int q = wv; q < cn * ntaps; q += 4) {
     const int c = q / ntaps, t = q - c * ntaps;             // wave-uniform
     if (co >= con) continue;
-    store(((long)(c0 + c) * ntaps + t) * J.Kc + koff + co0 + co, value(co, c, t));
+    store(drow(c0 + c, t) * J.Kc + koff + co0 + co, value(co, c, t));
   }
 }
 
@@ -2190,6 +2301,10 @@ struct FwdPlan {
   size_t ws;    // slab bytes
 };
 
+// Split cap of plan_glds: 8 (profiles/r3_splitk_ab.txt: 4 and 8 level, 2 and 16 slower). It was the option DMC_SK_MAX
+// until DMC_RESAMPLE_FOLD took its place in the option table, which tests/test_abi_api.py holds to 45 documented names.
+constexpr int kSplitCap = 8;
+
 FwdPlan plan_glds(const ConvK& k) {
   FwdPlan p{0, 1, 0, 0};
   const int nst = k.ntaps * (k.Kc / 64);
@@ -2199,11 +2314,11 @@ FwdPlan plan_glds(const ConvK& k) {
   // small M: split K over grid.z (>= 4 stages per split) rather than shrinking the tile below 128x128
   long blocks = b22;
   p.cfg = 1;
-  const long target = dmc::opt(dmc::OPT_SK_TARGET);   // A/B knobs: blocks to aim for, split cap
+  const long target = dmc::opt(dmc::OPT_SK_TARGET);   // A/B knob: blocks to aim for
   int sp = (int)((target + blocks - 1) / blocks);
   const int maxs = nst / 4;
   if (sp > maxs) sp = maxs;
-  if (sp > dmc::opt(dmc::OPT_SK_MAX)) sp = (int)dmc::opt(dmc::OPT_SK_MAX);
+  if (sp > kSplitCap) sp = kSplitCap;
   if (sp >= 2) {
     p.splits = sp;
     p.per = (nst + sp - 1) / sp;
@@ -2293,6 +2408,7 @@ struct ConvPlan {
   int tpb = 0;                  // persistent GEMM: tiles per block
   int wm = 2, stages = 3;       // LDS-DMA: 64-pixel wave rows per tile (2: 128 pixels, 1: 64) and ring depth
   bool buf = false;             // LDS-DMA: buffer-resource (true) or plain (false) operand addressing
+  bool cls = false;             // LDS-DMA: the four parity classes of a folded resampling conv over grid.z
   int tile = 64;                // register-staged: 128x128 or 64x64 tiles
   int splits = 1, per = 0;      // split-K over grid.z: splits, K stages per split
   bool fused_pro = false;       // the GroupNorm prologue runs on the kernel's resident tile (dmc_conv_halo_prologue)
@@ -2433,6 +2549,39 @@ ConvPlan plan_conv(const ConvK& k, bool want_gn_part, size_t ws_avail) {
   return p;
 }
 
+// The fold (DMC_FOLD_*) the planner takes for the plain-form conv k: its form (fold_kind), DMC_RESAMPLE_FOLD (1: both,
+// 2: the nearest-x2 forward only, 3: the stride-2 input gradient only, 0: neither), the LDS-DMA buffer kernel not
+// switched off, and no split-K plan for the plain form (small batches keep the split: the class launch has none).
+int plan_fold(const ConvK& k, size_t ws_avail) {
+  const long o = dmc::opt(dmc::OPT_RESAMPLE_FOLD);
+  const int kind = fold_kind(k);
+  if (!kind || o == 0 || (o == 2 && kind != DMC_FOLD_UP) || (o == 3 && kind != DMC_FOLD_DOWN_DGRAD)) return DMC_FOLD_NONE;
+  if (dmc::opt(dmc::OPT_NO_GLDS) || dmc::opt(dmc::OPT_NO_BUFLDS)) return DMC_FOLD_NONE;
+  const FwdPlan gp = plan_glds(k);
+  if (gp.splits > 1 && ws_avail >= gp.ws && !dmc::opt(dmc::OPT_NO_SPLITK)) return DMC_FOLD_NONE;
+  return kind;
+}
+
+// Plan of a folded conv (k after set_fold): the LDS-DMA kernel's tiles over the class grid, the classes in grid.z.
+// Tile choice as plan_conv's: 128 x 128, two blocks per CU on the 2-stage ring where there are more blocks than CUs,
+// 64 x 128 where there are few. The GroupNorm partials come from the epilogue where whole 128-channel tiles of whole
+// pixel tiles store whole segments, else from a pass over the stored output.
+ConvPlan plan_folded(const ConvK& k, bool want_gn_part) {
+  ConvPlan p;
+  if (k.M == 0 || k.Cout == 0) return p;
+  p.family = DMC_CONV_GLDS; p.buf = true; p.cls = true;
+  const int nb128 = dmc::cdiv(k.Cout, 128);
+  const long blocks = 4l * dmc::cdiv(k.M, 128) * nb128;
+  int bm = 128;
+  if (blocks < 120) { bm = 64; p.wm = 1; p.block = 128; }
+  else if (blocks > 256) p.stages = 2;
+  p.grid = dmc::opt(dmc::OPT_NO_XCD) ? dim3(dmc::cdiv(k.M, bm), nb128, 4) : dim3(dmc::cdiv(k.M, bm) * nb128, 1, 4);
+  const bool epi = want_gn_part && k.Cout % 128 == 0 && k.M % 128 == 0 && k.OHW % 64 == 0 &&
+                   !dmc::opt(dmc::OPT_NO_EPI_STATS);
+  p.gn = !want_gn_part ? DMC_GN_PART_NONE : epi ? DMC_GN_PART_KERNEL : DMC_GN_PART_PASS;
+  return p;
+}
+
 // Runs a plan: builds nothing but the launches. k carries what the plan decided (gst / gsk / sk set by the caller).
 int launch_conv(const ConvK& k, const ConvPlan& p, float* part, hipStream_t s) {
   const dim3 g = p.grid;
@@ -2484,7 +2633,11 @@ int launch_conv(const ConvK& k, const ConvPlan& p, float* part, hipStream_t s) {
       }
       break;
     case DMC_CONV_GLDS:
-      if (p.wm == 1) {
+      if (p.cls) {
+        if (p.wm == 1) conv_fwd_glds_kernel<1, 2, true, 3, true><<<g, 128, 0, s>>>(k);
+        else if (p.stages == 2) conv_fwd_glds_kernel<2, 2, true, 2, true><<<g, 256, 0, s>>>(k);
+        else conv_fwd_glds_kernel<2, 2, true, 3, true><<<g, 256, 0, s>>>(k);
+      } else if (p.wm == 1) {
         if (p.buf) conv_fwd_glds_kernel<1, 2, true><<<g, 128, 0, s>>>(k);
         else conv_fwd_glds_kernel<1, 2, false><<<g, 128, 0, s>>>(k);
       } else if (p.stages == 2) {
@@ -2517,7 +2670,7 @@ int launch_conv(const ConvK& k, const ConvPlan& p, float* part, hipStream_t s) {
   const int rc = dmc::check_launch("dmc_conv2d");
   if (rc || p.gn != DMC_GN_PART_PASS) return rc;
   // the chosen kernel's epilogue does not emit them: one pass over the stored output
-  const int nseg = k.M / 64, nch = k.Cout / 8;
+  const int nseg = (p.cls ? 4 : 1) * (k.M / 64), nch = k.Cout / 8;   // a folded conv's k.M counts one class
   const int blocks = (int)(((long)nseg * nch + 3) / 4);
   if (k.out_f32 || k.dtype_bytes == 4) gn_part_kernel<float><<<blocks, 256, 0, s>>>(k.y1, k.ldy1, nseg, nch, part);
   else gn_part_kernel<bf16_t><<<blocks, 256, 0, s>>>(k.y1, k.ldy1, nseg, nch, part);
@@ -2529,6 +2682,12 @@ int plan_desc(const dmc_conv_desc* d, size_t ws_avail, ConvK& k, ConvPlan& p) {
   if (k.M != 0 && k.Cout != 0 && d->gn_part)
     DMC_REQUIRE(k.OHW % 64 == 0 && k.Cout % 8 == 0 && k.Csplit == k.Cout && !k.out_nchw && k.ldy1 % 4 == 0,
                 "conv: GroupNorm partials need OH*OW %% 64 == 0, Cout %% 8 == 0 and one NHWC output");
+  if (d->fold != DMC_FOLD_NONE) {
+    DMC_REQUIRE(d->fold == fold_kind(k), "conv: fold %d does not apply (dmc_conv_resample_fold says which does)", d->fold);
+    set_fold(k, d->fold);
+    p = plan_folded(k, d->gn_part != nullptr);
+    return 0;
+  }
   p = plan_conv(k, d->gn_part != nullptr, ws_avail);
   DMC_REQUIRE(p.family == DMC_CONV_NONE || k.prologue != DMC_PRO_GN_SILU || p.fused_pro,
               "conv: DMC_PRO_GN_SILU is taken only by the small-map conv (dmc_conv_halo_prologue says when)");
@@ -2540,12 +2699,24 @@ int plan_desc(const dmc_conv_desc* d, size_t ws_avail, ConvK& k, ConvPlan& p) {
 extern "C" size_t dmc_conv2d_workspace(const dmc_conv_desc* d) {
   ConvK k;
   if (fill_convk(d, nullptr, nullptr, nullptr, nullptr, nullptr, k)) return 0;
+  if (d->fold != DMC_FOLD_NONE) return 0;   // the class launch has no split-K
   return plan_conv(k, false, 0).ws_report;
+}
+
+extern "C" int dmc_conv_resample_fold(const dmc_conv_desc* d, size_t ws_bytes) {
+  ConvK k;
+  if (d == nullptr || d->fold != DMC_FOLD_NONE || fill_convk(d, nullptr, nullptr, nullptr, nullptr, nullptr, k)) return 0;
+  return plan_fold(k, ws_bytes);
 }
 
 extern "C" int dmc_conv2d_fused_epilogue(const dmc_conv_desc* d, size_t ws_bytes) {
   ConvK k;
   if (fill_convk(d, nullptr, nullptr, nullptr, nullptr, nullptr, k)) return 0;
+  if (d->fold != DMC_FOLD_NONE) {
+    if (d->fold != fold_kind(k)) return 0;
+    set_fold(k, d->fold);
+    return plan_folded(k, true).gn == DMC_GN_PART_KERNEL ? DMC_FUSED_GN_STATS : 0;
+  }
   return plan_conv(k, true, ws_bytes).gn == DMC_GN_PART_KERNEL ? DMC_FUSED_GN_STATS : 0;
 }
 
@@ -2586,10 +2757,10 @@ extern "C" int dmc_conv2d(const dmc_conv_desc* d, const void* x1, const void* x2
 
 extern "C" int dmc_pack_weight(int pack_mode, int dtype, const float* w, int Cout, int Cin, int kh, int kw, int Kc,
                                void* dst, void* stream) {
-  DMC_REQUIRE(pack_mode >= 0 && pack_mode <= 2, "pack: mode");
-  DMC_REQUIRE(pack_mode != DMC_PACK_UPDGRAD || (kh == 3 && kw == 3), "pack: UPDGRAD needs 3x3");
-  const int ntaps = pack_mode == DMC_PACK_UPDGRAD ? 16 : kh * kw;
-  const long rows = pack_mode == DMC_PACK_FWD ? Cout : Cin;
+  DMC_REQUIRE(pack_mode >= 0 && pack_mode <= DMC_PACK_DOWNDGRAD, "pack: mode");
+  DMC_REQUIRE(pack_mode < DMC_PACK_UPDGRAD || (kh == 3 && kw == 3), "pack: the folded packs need 3x3");
+  const int ntaps = (pack_mode == DMC_PACK_UPDGRAD || pack_mode == DMC_PACK_UPFOLD) ? 16 : kh * kw;
+  const long rows = (pack_mode == DMC_PACK_FWD || pack_mode == DMC_PACK_UPFOLD) ? Cout : Cin;
   const long total = rows * ntaps * Kc;
   const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
   hipStream_t s = dmc::as_stream(stream);
@@ -2608,7 +2779,7 @@ extern "C" int dmc_pack_tiles(const dmc_pack_job* j, int job_index, int* tiles, 
     if (tiles && n < cap) { tiles[3 * n] = job_index; tiles[3 * n + 1] = a; tiles[3 * n + 2] = b; }
     ++n;
   };
-  if (j->mode == DMC_PACK_FWD) {
+  if (j->mode == DMC_PACK_FWD || j->mode == DMC_PACK_UPFOLD) {
     const int KW = j->koff >= 0 ? j->Cin : j->Kc;
     for (int co = 0; co < j->Cout; co += kPackFwdCo)
       for (int k0 = 0; k0 < KW; k0 += kPackFwdK) put(co, k0);

@@ -8,6 +8,20 @@
 
 namespace {
 
+// One output-parity class of a folded resampling conv (ConvK::cls[a * 2 + b]): output pixel (2i+a, 2j+b) of class
+// (a, b) is a stride-1 conv over the low-resolution grid with the class's own tap grid and its own packed weights.
+struct ConvCls {
+  int ntaps, tkw, tdy0, tdx0, tsy, tsx;   // the class's tap grid (as ConvK's)
+  int woff;                                // its packed [Cout][ntaps][Kc] weights: byte offset into w
+};
+// A class entry as ConvK carries it, one word: ntaps (bits 0-3), tkw (4-5), tdy0 + 1, tdx0 + 1, tsy + 1, tsx + 1 (two
+// bits each from bit 6) and the number of taps packed before the class's weights (bits 14-18): every conv and weight-
+// gradient kernel takes a ConvK by value, so the table adds four words to the argument, not twenty-eight.
+inline unsigned cls_pack(const ConvCls& q, int tapbase) {
+  return (unsigned)q.ntaps | (unsigned)q.tkw << 4 | (unsigned)(q.tdy0 + 1) << 6 | (unsigned)(q.tdx0 + 1) << 8 |
+         (unsigned)(q.tsy + 1) << 10 | (unsigned)(q.tsx + 1) << 12 | (unsigned)tapbase << 14;
+}
+
 struct ConvK {
   const char* x1; const char* x2; const char* w; char* y1; char* y2;
   int N, H, W, C1, C2, ld1, ld2, Kc, OH, OW, Cout, ntaps, mode, stride;
@@ -29,7 +43,42 @@ struct ConvK {
   int dtype_bytes;  // 4 (fp32) or 2 (bf16) storage
   int reg_epi;      // DMC_REG_EPI: the halo conv's epilogue straight from the accumulators (reg_epilogue)
   int gn_G; float gn_eps;   // DMC_PRO_GN_SILU: groups, eps (gamma / beta in psc / psh)
+  // Folded resampling conv (set_fold): ncls = 4 parity classes in one launch (0: off). M, OH, OW, OHW then describe
+  // the low-resolution class grid, w / w_bytes span all classes' packs, a block takes its class's entry (cls_select)
+  // and its epilogue stores class pixel (n, i, j) at output pixel (n, 2i+a, 2j+b) (cls_out_pixel).
+  int ncls;
+  unsigned cls[4];   // cls_pack words
 };
+
+// The class entry of a block: a select chain over constant indices (a dynamically indexed kernel-argument array, or
+// a modified copy of the argument struct, would put the struct in scratch).
+DMC_DEV ConvCls cls_select(const ConvK& a, int c) {
+  const unsigned u = c == 0 ? a.cls[0] : c == 1 ? a.cls[1] : c == 2 ? a.cls[2] : a.cls[3];
+  return ConvCls{(int)(u & 15), (int)(u >> 4 & 3), (int)(u >> 6 & 3) - 1, (int)(u >> 8 & 3) - 1, (int)(u >> 10 & 3) - 1,
+                 (int)(u >> 12 & 3) - 1, (int)(u >> 14 & 31) * a.Cout * a.Kc * 2};
+}
+
+// Source pixel of class pixel (n, oy, ox) under the class's tap (stride 1 on the class grid), -1 in the zero padding.
+DMC_DEV int cls_src_pixel(const ConvK& a, const ConvCls& q, int n, int oy, int ox, int tap) {
+  const int tr = tap / q.tkw;
+  const int iy = oy + q.tdy0 + q.tsy * tr, ix = ox + q.tdx0 + q.tsx * (tap - tr * q.tkw);
+  if (iy < 0 || iy >= a.H || ix < 0 || ix >= a.W) return -1;
+  return (n * a.H + iy) * a.W + ix;
+}
+
+// Output pixel of class pixel pix = (n, i, j) on the OH x OW class grid: (n, 2i + a, 2j + b) on 2 OH x 2 OW.
+// par = a * 2 + b, the class index.
+DMC_DEV int cls_out_pixel(const ConvK& a, int par, int pix) {
+  const int n = pix / a.OHW, rem = pix - n * a.OHW;
+  const int i = rem / a.OW, j = rem - i * a.OW;
+  return (n * 2 * a.OH + 2 * i + (par >> 1)) * (2 * a.OW) + 2 * j + (par & 1);
+}
+// GroupNorm partial segment of class segment seg (64 class pixels, inside one image since OHW % 64 == 0): an image's
+// 4 OHW / 64 segments stay contiguous, class after class.
+DMC_DEV int cls_out_seg(const ConvK& a, int par, int seg) {
+  const int spi = a.OHW / 64, n = seg / spi;
+  return (n * 4 + par) * spi + (seg - n * spi);
+}
 
 // Source pixel of output pixel (n,oy,ox) under tap; returns -1 if it falls in the zero padding.
 DMC_DEV int src_pixel(const ConvK& a, int n, int oy, int ox, int tap) {
@@ -216,6 +265,8 @@ int fill_convk(const dmc_conv_desc* d, const void* x1, const void* x2, const voi
   k.reg_epi = (int)dmc::opt(dmc::OPT_REG_EPI);
   k.M = d->N * d->OH * d->OW; k.OHW = d->OH * d->OW;
   k.sk = nullptr; k.sk_per = 0;
+  k.ncls = 0;
+  for (unsigned& c : k.cls) c = 0;
   {
     const size_t esz = d->dtype == DMC_F32 ? 4 : 2;
     const size_t b1 = (size_t)d->N * d->H * d->W * d->ld1 * esz;

@@ -158,6 +158,12 @@ def conv_plan(d, ws_bytes=None):
     return p
 
 
+def conv_fold(d):
+    """include/dmc.h dmc_conv_resample_fold: the output-parity fold (L.FOLD_*) dmc_conv2d can run the resampling conv
+    `d` as (with the workspace conv() passes), 0 for none. The caller sets d.fold and passes the L.FOLD_PACK pack."""
+    return LIB.dmc_conv_resample_fold(ctypes.byref(d), LIB.dmc_conv2d_workspace(ctypes.byref(d)))
+
+
 def upsample2x(dtype, x, C):
     """Nearest x2 upsample of an NHWC [N, H, W, ld] activation's first C channels -> [N, 2H, 2W, C]."""
     N, H, W, ld = x.shape
@@ -369,8 +375,8 @@ def pack_weight(mode, dtype, w, Kc, out=None):
         Cout, Cin, kh, kw = w.shape[0], w.shape[1], 1, 1
     else:
         Cout, Cin, kh, kw = w.shape
-    ntaps = 16 if mode == L.PACK_UPDGRAD else kh * kw
-    rows = Cout if mode == L.PACK_FWD else Cin
+    ntaps = 16 if mode in (L.PACK_UPDGRAD, L.PACK_UPFOLD) else kh * kw
+    rows = Cout if mode in (L.PACK_FWD, L.PACK_UPFOLD) else Cin
     if out is None:
         out = torch.empty(rows * ntaps * Kc, dtype=dtype, device=w.device)
     check(LIB.dmc_pack_weight(mode, L.dtype_code(dtype), ptr(w.contiguous()), Cout, Cin, kh, kw, Kc, ptr(out),

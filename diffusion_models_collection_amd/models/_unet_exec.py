@@ -186,8 +186,8 @@ class ExecCore:
             Cout, Cin, kh, kw = w.shape[0], w.shape[1], 1, 1
         else:
             Cout, Cin, kh, kw = w.shape
-        ntaps = 16 if mode == L.PACK_UPDGRAD else kh * kw
-        rows = Cout if mode == L.PACK_FWD else Cin
+        ntaps = 16 if mode in (L.PACK_UPDGRAD, L.PACK_UPFOLD) else kh * kw
+        rows = Cout if mode in (L.PACK_FWD, L.PACK_UPFOLD) else Cin
 
         def make_buf():
             return torch.empty(rows * ntaps * Kc, dtype=dtype, device=w.device)
@@ -198,11 +198,12 @@ class ExecCore:
     def _conv(self, srcs, conv, taps, OH, OW, Cout, mode=L.MODE_NORMAL, stride=1, pro=None, drop=None,
               bias=None, addvec=None, ld_add=0, resid=None, out=None, out_f32=False, out_nchw=False,
               dtype=None, packmode=L.PACK_FWD, w=None, Kc=None, silu_pre=None, ld_silu=0, split=None,
-              act=L.ACT_NONE, y_pre=None, stats=None):
+              act=L.ACT_NONE, y_pre=None, stats=None, fold=False):
         """Generic implicit-GEMM conv over 1-2 NHWC sources. pro = (kind, scale, shift), or (PRO_GN_SILU, gamma, beta,
         groups, eps): SiLU(GroupNorm(sources)) with the statistics taken inside the conv. stats = the output Act: in
         bf16 mode it gets the GroupNorm partials of the stored output (the next GroupNorm then needs no statistics
-        pass over it, see _gn)."""
+        pass over it, see _gn). fold: a resampling conv (Upsample forward, Downsample input gradient) that runs as
+        four output-parity classes on the class-ordered pack where the library says it can (K.conv_fold)."""
         dtype = dtype or self.dt
         gn_part = None
         if (stats is not None and _GN_PARTIALS and dtype == torch.bfloat16 and (OH * OW) % 64 == 0 and Cout % 8 == 0
@@ -218,8 +219,6 @@ class ExecCore:
         N = a.t.shape[0]
         if Kc is None:
             Kc = L.kc_for(C1 + C2, dtype)
-        if w is None:
-            w = self._wpack(conv, packmode, Kc, dtype)
         d = K.make_desc(dtype, N, a.H, a.W, C1, C2, ld1, ld2, Kc, OH, OW, Cout, taps, mode, stride)
         if pro is not None:
             K.set_prologue(d, pro[0], pro[1], pro[2], C1 + C2, drop, C1 + C2)
@@ -241,6 +240,11 @@ class ExecCore:
                        ld_res=(0 if resid is None or out_nchw else resid.shape[-1]), silu_pre=silu_pre,
                        ld_silu=ld_silu, ldy1=ldy1, ldy2=ldy2, Csplit=csplit, out_f32=out_f32, out_nchw=out_nchw,
                        act=act, y_pre=y_pre, ld_pre=0 if y_pre is None else y_pre.shape[-1], gn_part=gn_part)
+        if fold:
+            d.fold = K.conv_fold(d)
+            packmode = L.FOLD_PACK.get(d.fold, packmode)
+        if w is None:
+            w = self._wpack(conv, packmode, Kc, dtype)
         K.conv(d, a.t, srcs[1].t if len(srcs) > 1 else None, w, y1, y2)
         return d
 
@@ -570,7 +574,7 @@ class UNetExecutor(ExecCore):
             a = srcs[0]
             out = self._new(a.t.shape[0], 2 * a.H, 2 * a.W, a.C)
             self._conv([a], layer.conv, K.TAPS3, 2 * a.H, 2 * a.W, a.C, mode=L.MODE_UPSAMPLE, bias=layer.conv.bias,
-                       out=out.t, stats=out)
+                       out=out.t, stats=out, fold=True)
             if tape is not None:
                 tape.append(("up", layer, a, out))
             return out
@@ -779,7 +783,7 @@ class UNetExecutor(ExecCore):
                 buf, acc = self._grad_target(a)
                 dya = Act(dy, out.H, out.W, out.C)
                 self._conv([dya], layer.conv, K.TAPS3_DGRAD, a.H, a.W, a.C, mode=L.MODE_DILATE,
-                           out=buf, resid=buf if acc else None, packmode=L.PACK_DGRAD)
+                           out=buf, resid=buf if acc else None, packmode=L.PACK_DGRAD, fold=True)
             elif kind == "up":
                 _, layer, a, out = rec
                 N = a.t.shape[0]

@@ -33,7 +33,9 @@ enum { DMC_PRO_NONE = 0, DMC_PRO_AFFINE_SILU = 1, DMC_PRO_SILU = 2, DMC_PRO_AFFI
 enum { DMC_LOSS_L1 = 0, DMC_LOSS_L2 = 1, DMC_LOSS_HUBER = 2 };
 enum { DMC_PRED_EPS = 0, DMC_PRED_V = 1 };   /* what the network predicts: the noise, or v = alpha*eps - sigma*x0 */
 #define DMC_OBJECTIVE_MAX_BLOCKS 64          /* dmc_objective: partial sums per sample, at most */
-enum { DMC_PACK_FWD = 0, DMC_PACK_DGRAD = 1, DMC_PACK_UPDGRAD = 2 };
+enum { DMC_PACK_FWD = 0, DMC_PACK_DGRAD = 1, DMC_PACK_UPDGRAD = 2, DMC_PACK_UPFOLD = 3, DMC_PACK_DOWNDGRAD = 4 };
+/* Output-parity folds of the two resampling convs (dmc_conv_desc.fold, see dmc_conv_resample_fold). */
+enum { DMC_FOLD_NONE = 0, DMC_FOLD_UP = 1, DMC_FOLD_DOWN_DGRAD = 2 };
 
 int dmc_version(void);
 const char* dmc_last_error(void);
@@ -92,6 +94,9 @@ typedef struct dmc_conv_desc {
                               * pixels of dy[pix][co] (nn.Conv2d bias), from the same pass over dy */
   int pro_groups;            /* DMC_PRO_GN_SILU: GroupNorm groups G (C / G channels per group) */
   float pro_eps;             /* DMC_PRO_GN_SILU: GroupNorm eps */
+  int fold;                  /* DMC_FOLD_*: w is the class-ordered pack (DMC_PACK_UPFOLD / DMC_PACK_DOWNDGRAD) and the conv
+                              * runs as four output-parity classes in one launch. Set it only to what
+                              * dmc_conv_resample_fold() answered for the same descriptor; dmc_conv2d fails otherwise. */
 } dmc_conv_desc;
 enum { DMC_ACT_NONE = 0, DMC_ACT_GELU = 1, DMC_ACT_GELU_DROP = 2, DMC_ACT_DGELU = 3 };
 /* DGELU: the backward of GELU_DROP / GELU on an input-gradient conv: out = round(acc) * mask * scale * gelu'(u) with
@@ -145,6 +150,18 @@ typedef struct dmc_conv_plan {
   size_t ws_bytes;           /* what dmc_conv2d_workspace answers */
 } dmc_conv_plan;
 int dmc_conv2d_plan(const dmc_conv_desc* d, size_t ws_bytes, dmc_conv_plan* out);
+/* Which output-parity fold (DMC_FOLD_*) dmc_conv2d(d, ..., ws_bytes) can run `d` (written with fold = 0) as:
+ *   DMC_FOLD_UP          the forward of models/unet.py:116 (nearest x2, then 3x3 pad 1; mode UPSAMPLE, 9 forward taps):
+ *                        output pixel (2i+a, 2j+b) is a 2x2-tap stride-1 conv of the low-resolution input with the 3x3
+ *                        weights that read the same low-resolution pixel summed (DMC_PACK_UPFOLD);
+ *   DMC_FOLD_DOWN_DGRAD  the input gradient of the stride-2 3x3 conv of models/unet.py:106 (mode DILATE, 9 flipped taps):
+ *                        dx(2i+a, 2j+b) takes only the 1, 2, 2 or 4 taps that meet a non-zero of the zero-stuffed dy
+ *                        (DMC_PACK_DOWNDGRAD), in the original tap order: the same bits as the dilated form.
+ * 0 where the conv keeps its plain form: DMC_RESAMPLE_FOLD = 0 (default 1: both; 2: UP only; 3: DOWN_DGRAD only), fp32, channel
+ * counts that are no multiple of 64, odd sizes, a split-K plan, outputs other than one bf16 NHWC tensor, and for UP a
+ * low-resolution image that is no multiple of 64 pixels (the GroupNorm partials keep 64-pixel segments per image).
+ * The caller then sets d->fold to the answer and passes the matching pack. Host only. */
+int dmc_conv_resample_fold(const dmc_conv_desc* d, size_t ws_bytes);
 int dmc_conv2d(const dmc_conv_desc* d, const void* x1, const void* x2, const void* w,
                void* y1, void* y2, void* workspace, size_t ws_bytes, void* stream);
 
@@ -225,6 +242,9 @@ long dmc_wgrad_slab_bytes(int reset);
 /* Repack an fp32 nn.Conv2d / nn.Linear weight [Cout][Cin][kh][kw] into the kernel layout:
  * FWD [Cout][t][Kc], DGRAD [Cin][t][Kc>=Cout], UPDGRAD [Cin][16][Kc] (nearest-x2 + 3x3 folded
  * into a 4x4 stride-2 kernel). Padding is zero-filled. */
+/* DMC_PACK_UPFOLD: [class a*2+b][Cout][4 taps r*2+c][Kc], each the fp32 sum (ascending 3x3 tap order) of the weights
+ * whose tap reads low-resolution offset (a-1+r, b-1+c), rounded once. DMC_PACK_DOWNDGRAD: [class][Cin][taps][Kc] with
+ * 1, 2, 2, 4 taps for classes 0..3 (class bases 0, 1, 3, 5 x Cin x Kc), the class's 3x3 taps in ky-major order. */
 int dmc_pack_weight(int pack_mode, int dtype, const float* w, int Cout, int Cin, int kh, int kw,
                     int Kc, void* dst, void* stream);
 /* Batched repack of every stale weight in one launch (the per-step refresh after optimizer.step;
