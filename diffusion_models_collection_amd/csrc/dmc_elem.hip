@@ -12,7 +12,8 @@
 //   EMA                 utils/trainer.py:187-202
 //   clip_grad_norm_     utils/trainer.py:259
 // Not in the reference: the DPM-Solver++ step (arXiv:2211.01095) and the v-prediction / min-SNR objective with its
-// output conversion (arXiv:2202.00512, arXiv:2303.09556), written to the same one-rounding-per-op rule.
+// output conversion (arXiv:2202.00512, arXiv:2303.09556), written to the same one-rounding-per-op rule, and the
+// variational-bound step of the bits-per-dimension evaluation (arXiv:2006.11239, arXiv:2102.09672).
 #include <stdlib.h>
 #include <string.h>
 #include "dmc_common.h"
@@ -356,6 +357,141 @@ __global__ __launch_bounds__(256) void pred_convert_kernel(const float* x, const
       }
     }
   }
+}
+
+// ---------------- variational bound (bits per dimension): one timestep's terms and the next x_t in one pass ----------------
+// Ho et al. 2020 (arXiv:2006.11239 §3-4), Nichol & Dhariwal 2021 (arXiv:2102.09672 §2-3); the host table is
+// diffusion/_vlb.py: row {c_x, c_p, kprec, kvar, keps, isig}. The KL of the two posteriors is kvar + kprec*(x0 - x0_pred)^2:
+// their means differ by c1*(x0 - x0_pred) exactly and are never formed (formed first they cancel at the noisy end).
+struct VlbRow {
+  float cx, cp, kprec, kvar, isig;
+};
+
+// Exact normal CDF (not the tanh approximation of some public implementations).
+DMC_DEV float vlb_cdf(float z) { return 0.5f * erfcf(-z * 0.70710678118654752f); }
+
+// -log p of one element under the decoder's Gaussian discretised on the 8-bit grid k/127.5 - 1; d = x0 - mean
+DMC_DEV float vlb_decoder(float x0, float d, float isig) {
+  const float h = 1.0f / 255.0f;
+  const float zp = (d + h) * isig;
+  const float zm = (d - h) * isig;
+  float pr;
+  if (x0 < -0.999f) pr = vlb_cdf(zp);
+  else if (x0 > 0.999f) pr = vlb_cdf(-zm);
+  else if (zm <= 0.f) pr = vlb_cdf(zp) - vlb_cdf(zm);
+  else pr = vlb_cdf(-zm) - vlb_cdf(-zp);      // both values below 1/2: the difference keeps its digits
+  return -logf(fmaxf(pr, 1e-12f));
+}
+
+struct VlbSums {
+  float term, dd, du, xx;
+};
+
+// u = c_x*x_t - c_p*pred is the x0 prediction as fp32 holds it. x0 - u is formed without u's rounding, as
+// (x0 - c_x*x_t) + c_p*pred plus the two products' rounding errors (exact, by fma): where the prediction is good the
+// difference is small against x0 and would otherwise keep only its leading digits.
+DMC_DEV void vlb_elem(const VlbRow& r, bool dec, int clip, float x0, float xt, float p, VlbSums& s) {
+  const float a_ = r.cx * xt;
+  const float ae = fmaf(r.cx, xt, -a_);
+  const float b_ = r.cp * p;
+  const float be = fmaf(r.cp, p, -b_);
+  const float u = a_ - b_;
+  const float du = ((x0 - a_) + b_) + (be - ae);
+  float d = du;
+  if (clip && u > 1.f) d = x0 - 1.f;
+  if (clip && u < -1.f) d = x0 + 1.f;
+  const float d2 = d * d;
+  s.term += dec ? vlb_decoder(x0, d, r.isig) : r.kvar + r.kprec * d2;
+  s.dd += d2;
+  s.du += du * du;
+  s.xx += x0 * x0;
+}
+
+// Grid as objective_kernel: blockIdx.y strides over samples, blockIdx.x over the sample's elements, so t, the row and
+// the decoder branch are block-uniform. Block (bx, n) leaves its four sums at partial[(n * gridDim.x + bx) * 4 ..].
+// x0, x_t and pred are read once; with x_next, z_next is read and x_next written in the same pass (dmc_q_sample's ops).
+template <bool VEC>
+__global__ __launch_bounds__(256) void vlb_step_kernel(const float* x0, const float* xt, const float* pred,
+                                                       const int64_t* t, const float* coef, int T, int clip,
+                                                       const float* zn, const int64_t* t_next, const float* sa,
+                                                       const float* s1, int N, int per, float* x_next,
+                                                       float* partial) {
+  __shared__ float red[4][4];
+  for (int n = blockIdx.y; n < N; n += gridDim.y) {
+    const long tt = clamp_t(t[n], T);
+    const float* c = coef + tt * 6;
+    const VlbRow r{c[0], c[1], c[2], c[3], c[5]};
+    const bool dec = tt == 0;
+    bool fwd = false;
+    float an = 0.f, bn = 0.f;
+    if (x_next != nullptr && t_next[n] >= 0) {
+      const long tn = clamp_t(t_next[n], T);
+      fwd = true;
+      an = sa[tn];
+      bn = s1[tn];
+    }
+    const size_t base = (size_t)n * per;
+    VlbSums s{0.f, 0.f, 0.f, 0.f};
+    if (VEC) {
+      const int per4 = per / 4;
+      for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < per4; q += gridDim.x * blockDim.x) {
+        const size_t i = base + (size_t)q * 4;
+        const v4f xv = *(const v4f*)(x0 + i);
+        const v4f tv = *(const v4f*)(xt + i);
+        const v4f pv = *(const v4f*)(pred + i);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) vlb_elem(r, dec, clip, xv[k], tv[k], pv[k], s);
+        if (fwd) {
+          const v4f zv = *(const v4f*)(zn + i);
+          v4f ov;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const float u = an * xv[k];
+            const float v = bn * zv[k];
+            ov[k] = u + v;
+          }
+          *(v4f*)(x_next + i) = ov;
+        }
+      }
+    } else {
+      for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < per; q += gridDim.x * blockDim.x) {
+        const size_t i = base + q;
+        const float xx = x0[i];
+        vlb_elem(r, dec, clip, xx, xt[i], pred[i], s);
+        if (fwd) {
+          const float u = an * xx;
+          const float v = bn * zn[i];
+          x_next[i] = u + v;
+        }
+      }
+    }
+    float v[4] = {wave_sum(s.term), wave_sum(s.dd), wave_sum(s.du), wave_sum(s.xx)};
+    if ((threadIdx.x & 63) == 0)
+      for (int k = 0; k < 4; ++k) red[k][threadIdx.x >> 6] = v[k];
+    __syncthreads();
+    if (threadIdx.x < 4) {
+      const float* rk = red[threadIdx.x];
+      partial[((size_t)n * gridDim.x + blockIdx.x) * 4 + threadIdx.x] = (rk[0] + rk[1]) + (rk[2] + rk[3]);
+    }
+    __syncthreads();   // red is reused by the block's next sample
+  }
+}
+
+// Thread n adds sample n's partials in block order: a fixed order, no atomics.
+__global__ __launch_bounds__(256) void vlb_final_kernel(const float* partial, int gx, const int64_t* t,
+                                                        const float* coef, int T, int N, int per, float* vb,
+                                                        float* xstart_mse, float* eps_mse, float* x0_sq) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  float s[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int b = 0; b < gx; ++b)
+    for (int k = 0; k < 4; ++k) s[k] += partial[((size_t)n * gx + b) * 4 + k];
+  const float keps = coef[clamp_t(t[n], T) * 6 + 4];
+  const float fp = (float)per;
+  vb[n] = (s[0] / fp) / 0.69314718055994531f;
+  xstart_mse[n] = s[1] / fp;
+  eps_mse[n] = keps * (s[2] / fp);
+  x0_sq[n] = s[3] / fp;
 }
 
 // ---------------- samplers ----------------
@@ -944,6 +1080,28 @@ extern "C" int dmc_pred_convert(int pred_type, const float* x, const int64_t* t,
   if (vec) pred_convert_kernel<true><<<grid, 256, 0, s>>>(x, t, sa, s1, T, pred, reps, N, per, eps_out, x0_out);
   else pred_convert_kernel<false><<<grid, 256, 0, s>>>(x, t, sa, s1, T, pred, reps, N, per, eps_out, x0_out);
   return dmc::check_launch("dmc_pred_convert");
+}
+
+extern "C" int dmc_vlb_step(const float* x0, const float* x_t, const float* pred, const int64_t* t, const float* coef,
+                            int T, int clip, const float* z_next, const int64_t* t_next, const float* sa, const float* s1,
+                            int N, int per, float* x_next, float* vb, float* xstart_mse, float* eps_mse, float* x0_sq,
+                            float* ws, void* stream) {
+  DMC_REQUIRE(T > 0 && N > 0 && per > 0, "vlb_step: T %d, N %d, per_sample %d must be positive", T, N, per);
+  DMC_REQUIRE(x0 && x_t && pred && t && coef && vb && xstart_mse && eps_mse && x0_sq && ws,
+              "vlb_step: only x_next and its operands z_next, t_next, sa, s1 may be NULL");
+  DMC_REQUIRE(!x_next || (z_next && t_next && sa && s1), "vlb_step: x_next needs z_next, t_next and both tables");
+  const uintptr_t bits = (uintptr_t)x0 | (uintptr_t)x_t | (uintptr_t)pred | (uintptr_t)x_next |
+                         (x_next ? (uintptr_t)z_next : 0);   // a NULL or unread operand adds no bits
+  const bool vec = per % 4 == 0 && (bits & 15) == 0;
+  const dim3 grid = sample_grid(vec ? per / 4 : per, N, DMC_VLB_MAX_BLOCKS);
+  hipStream_t s = dmc::as_stream(stream);
+  if (vec)
+    vlb_step_kernel<true><<<grid, 256, 0, s>>>(x0, x_t, pred, t, coef, T, clip, z_next, t_next, sa, s1, N, per, x_next, ws);
+  else
+    vlb_step_kernel<false><<<grid, 256, 0, s>>>(x0, x_t, pred, t, coef, T, clip, z_next, t_next, sa, s1, N, per, x_next,
+                                                ws);
+  vlb_final_kernel<<<(N + 255) / 256, 256, 0, s>>>(ws, (int)grid.x, t, coef, T, N, per, vb, xstart_mse, eps_mse, x0_sq);
+  return dmc::check_launch("dmc_vlb_step");
 }
 
 extern "C" int dmc_ddim_step(const float* x, const float* eps, const float* x0_in, const int64_t* t, const int64_t* t_next,

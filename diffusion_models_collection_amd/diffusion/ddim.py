@@ -14,6 +14,8 @@ prediction_type='v' (not in the reference; ddpm.py ObjectiveMixin): one dmc_pred
 hands eps and x0 to the same step kernel.
 img2img / inpaint (not in the reference; _edit_loop.EditMixin) run the same steps from, or around, a given image;
 invert runs the eta = 0 step with (t, t_next) swapped, from an image up to its latent.
+calc_bpd (not in the reference; _likelihood.LikelihoodMixin) is the variational bound over all T timesteps, whatever
+the number of inference steps.
 """
 import os
 
@@ -24,10 +26,11 @@ from .. import kernels as K
 from . import _objective, _schedule
 from ._edit_loop import EditMixin
 from ._graph import StepGraph, cache_for, run_loop
+from ._likelihood import LikelihoodMixin
 from .ddpm import ObjectiveMixin, _require_cuda, diffusion_loss, make_betas
 
 
-class DDIM(ObjectiveMixin, EditMixin):
+class DDIM(ObjectiveMixin, EditMixin, LikelihoodMixin):
     """DDIM diffusion process with accelerated sampling (diffusion/ddim.py:13-351)."""
 
     def __init__(self, num_timesteps=1000, num_inference_steps=50, beta_start=0.0001, beta_end=0.02,

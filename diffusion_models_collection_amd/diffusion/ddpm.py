@@ -20,7 +20,8 @@ p_sample(noise=...), sample(x_T=...), sample_with_cfg(x_T=...) inject the Gaussi
 DDPM(prediction_type='v') trains and samples a v-prediction network (arXiv:2202.00512), p_losses(snr_gamma=...)
 weights each sample by min-SNR-gamma (arXiv:2303.09556); see _objective.py. With the defaults neither launches
 anything new. img2img / inpaint (not in the reference either; _edit_loop.EditMixin, _edit.py, dmc_known_blend) run the
-steps of sample / sample_with_cfg from, or around, a given image.
+steps of sample / sample_with_cfg from, or around, a given image. calc_bpd (not in the reference; _likelihood.LikelihoodMixin,
+_vlb.py, dmc_vlb_step) evaluates the variational bound in bits per dimension.
 """
 import numpy as np
 import torch
@@ -31,6 +32,7 @@ from .. import kernels as K
 from . import _objective, _schedule
 from ._edit_loop import EditMixin
 from ._graph import StepGraph, run_loop
+from ._likelihood import LikelihoodMixin
 
 
 def make_betas(num_timesteps, beta_start, beta_end, beta_schedule):
@@ -142,7 +144,7 @@ class ObjectiveMixin:
         return eps[:B], eps[B:]
 
 
-class DDPM(ObjectiveMixin, EditMixin):
+class DDPM(ObjectiveMixin, EditMixin, LikelihoodMixin):
     """DDPM diffusion process (diffusion/ddpm.py:15-332)."""
 
     def __init__(self, num_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule='linear', device='cuda',

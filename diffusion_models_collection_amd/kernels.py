@@ -723,6 +723,46 @@ def pred_convert(pred_type, x, t, sa, s1, pred, want_x0=True, out=None):
     return eps, x0
 
 
+def vlb_step(x0, x_t, pred, t, coef, clip=True, z_next=None, t_next=None, sa=None, s1=None, x_next=None, out=None):
+    """One timestep of the variational bound (dmc_vlb_step): t[n] picks sample n's row {c_x, c_p, kprec, kvar, keps,
+    isig} of the [T, 6] table (diffusion/_vlb.py). Returns (vb, xstart_mse, eps_mse, x0_sq), [N] fp32 each; out: the
+    four buffers to fill. With x_next (a buffer of x0's shape), samples with t_next >= 0 get
+    x_next = sa[t_next]*x0 + s1[t_next]*z_next in the same pass; the others are not written."""
+    what = "dmc_vlb_step"
+    if not x0.is_cuda or x0.dim() < 1 or x0.numel() < 1:
+        raise L.DMCError(f"{what}: x0 must be a non-empty device tensor, got {tuple(x0.shape)} on {x0.device}")
+    N = x0.shape[0]
+    dev = x0.device
+    _same(x0, x_t, pred, z_next, x_next, what=what)
+    _fp32_contig(what, x0, x_t, pred, z_next, x_next)
+    if t is None:
+        raise L.DMCError(f"{what}: needs timesteps")
+    _steps(N, dev, t, t_next, what=what)
+    if (coef.dim() != 2 or coef.shape[1] != 6 or coef.shape[0] < 1 or coef.dtype != torch.float32
+            or coef.device != dev or not coef.is_contiguous()):
+        raise L.DMCError(f"{what}: coef must be a contiguous fp32 [T, 6] tensor on {dev}, got "
+                         f"{coef.dtype} {tuple(coef.shape)} on {coef.device}")
+    T = coef.shape[0]
+    if x_next is not None:
+        if z_next is None or t_next is None or _tables(what, dev, sa, s1) != T or sa is None or s1 is None:
+            raise L.DMCError(f"{what}: x_next needs z_next, t_next and the [T = {T}] sqrt_alphas_cumprod / "
+                             "sqrt_one_minus_alphas_cumprod tables")
+    rows = out if out is not None else tuple(torch.empty(N, dtype=torch.float32, device=dev) for _ in range(4))
+    if len(rows) != 4:
+        raise L.DMCError(f"{what}: out must hold the four [N] buffers vb, xstart_mse, eps_mse, x0_sq")
+    for r in rows:
+        if r.shape != (N,) or r.device != dev:
+            raise L.DMCError(f"{what}: an output row is {tuple(r.shape)} on {r.device}, expected ({N},) on {dev}")
+    _fp32_contig(what, *rows)
+    ws = SCRATCH.get(4 * L.VLB_MAX_BLOCKS * N * 4, dev)
+    nxt = x_next is not None
+    check(LIB.dmc_vlb_step(ptr(x0), ptr(x_t), ptr(pred), ptr(t), ptr(coef), T, int(bool(clip)),
+                           ptr(z_next) if nxt else None, ptr(t_next) if nxt else None, ptr(sa) if nxt else None,
+                           ptr(s1) if nxt else None, N, x0.numel() // N, ptr(x_next), ptr(rows[0]), ptr(rows[1]),
+                           ptr(rows[2]), ptr(rows[3]), ptr(ws), L.stream()), what)
+    return tuple(rows)
+
+
 def ddim_step(x, eps, t, t_next, alphas_cumprod, eta=0.0, clip=True, x0=None, z=None, out=None):
     if out is None:
         out = torch.empty_like(x)

@@ -791,6 +791,46 @@ class DiffusionTrainer:
             swanlab.log({'samples': swanlab.Image(samples)}, step=epoch)
         return samples
 
+    @torch.no_grad()
+    def evaluate_bpd(self, loader, max_batches=None, use_ema=True, **calc_bpd_kwargs):
+        """Variational bound in bits per dimension over `loader` (not in the reference; diffusion.calc_bpd): batches
+        of (images, labels) or bare images, labels shifted by +1 on a conditional model as train_step does. Runs the EMA
+        model when there is one and use_ema is set, in eval mode, and restores the model's mode. Returns the
+        image-weighted means {'total_bpd', 'prior_bpd', 'vb' ([S] per timestep walked), 'num_images'}; total_bpd is
+        None when calc_bpd was given a subset of the timesteps."""
+        model = self.ema_model if (use_ema and self.ema_model is not None) else self._module
+        was_training = model.training
+        model.eval()
+        total = prior = vb = None
+        n = 0
+        try:
+            for i, batch in enumerate(loader):
+                if max_batches is not None and i >= max_batches:
+                    break
+                labels = None
+                if isinstance(batch, (list, tuple)):
+                    images = batch[0]
+                    if self.conditional and len(batch) > 1:
+                        labels = batch[1].to(self.device) + 1
+                else:
+                    images = batch
+                images = images.to(self.device, non_blocking=True)
+                out = self.diffusion.calc_bpd(model, images, y=labels, **calc_bpd_kwargs)
+                sums = (out["total_bpd"], out["prior_bpd"], out["vb"])
+                sums = [None if s is None else s.double().sum(0) for s in sums]
+                if n == 0:
+                    total, prior, vb = sums
+                else:
+                    total = None if total is None or sums[0] is None else total + sums[0]
+                    prior, vb = prior + sums[1], vb + sums[2]
+                n += images.shape[0]
+        finally:
+            model.train(was_training)
+        if n == 0:
+            raise ValueError("evaluate_bpd: the loader gave no batch")
+        return {'total_bpd': None if total is None else total.item() / n, 'prior_bpd': prior.item() / n,
+                'vb': (vb / n).float().cpu(), 'num_images': n}
+
     def save_checkpoint(self, epoch, is_best=False):
         if not self.is_main_process:
             return

@@ -33,6 +33,8 @@ enum { DMC_PRO_NONE = 0, DMC_PRO_AFFINE_SILU = 1, DMC_PRO_SILU = 2, DMC_PRO_AFFI
 enum { DMC_LOSS_L1 = 0, DMC_LOSS_L2 = 1, DMC_LOSS_HUBER = 2 };
 enum { DMC_PRED_EPS = 0, DMC_PRED_V = 1 };   /* what the network predicts: the noise, or v = alpha*eps - sigma*x0 */
 #define DMC_OBJECTIVE_MAX_BLOCKS 64          /* dmc_objective: partial sums per sample, at most */
+#define DMC_VLB_MAX_BLOCKS 64                /* dmc_vlb_step: blocks per sample, at most (four partial sums each) */
+#define DMC_VLB_WORKSPACE_FLOATS(N) (4 * DMC_VLB_MAX_BLOCKS * (size_t)(N))   /* dmc_vlb_step's workspace */
 enum { DMC_PACK_FWD = 0, DMC_PACK_DGRAD = 1, DMC_PACK_UPDGRAD = 2, DMC_PACK_UPFOLD = 3, DMC_PACK_DOWNDGRAD = 4 };
 /* Output-parity folds of the two resampling convs (dmc_conv_desc.fold, see dmc_conv_resample_fold). */
 enum { DMC_FOLD_NONE = 0, DMC_FOLD_UP = 1, DMC_FOLD_DOWN_DGRAD = 2 };
@@ -403,6 +405,34 @@ int dmc_objective(int pred_type, int loss_type, const float* pred, const float* 
 int dmc_pred_convert(int pred_type, const float* x, const int64_t* t, const float* sa, const float* s1,
                      int T, const float* pred, int reps, int N, int per_sample, float* eps_out,
                      float* x0_out, void* stream);
+/* One timestep of the variational bound on the log-likelihood, in bits per dimension, and the next step's x_t in
+ * ONE pass; not in the reference (Ho et al. 2020, arXiv:2006.11239 §3-4; Nichol & Dhariwal 2021, arXiv:2102.09672
+ * §2-3). coef: [T][6] fp32 rows {c_x, c_p, kprec, kvar, keps, isig} (diffusion/_vlb.py); t[n], clamped into [0, T),
+ * picks sample n's row. x0, x_t, pred, z_next, x_next: [N][per_sample] fp32. Per element of sample n:
+ *   u  = c_x*x_t - c_p*pred                 -- the x0 prediction, unclipped ('eps' and 'v' differ in the table only)
+ *   xp = clip ? clamp(u, -1, 1) : u;   d = x0 - xp;   du = x0 - u
+ *   du (and d where the clip does not act) is formed without u's rounding, as (x0 - c_x*x_t) + c_p*pred plus the two
+ *   products' rounding errors (fma): a good prediction's small error keeps its digits instead of an ulp of x0
+ *   t > 0:   term = kvar + kprec*d*d        -- KL(q(x_{t-1}|x_t,x0) || p(x_{t-1}|x_t)): the two means differ by
+ *                                              c1*(x0 - xp) exactly and are never formed, so nothing cancels
+ *   t == 0:  term = -lp, the decoder's Gaussian discretised on the 8-bit grid with the EXACT normal CDF
+ *            Phi(z) = 0.5*erfc(-z/sqrt 2), deliberately not the tanh approximation of some public implementations:
+ *              zp = (d + 1/255)*isig;  zm = (d - 1/255)*isig
+ *              lp = log(max(Phi(zp), 1e-12))            if x0 < -0.999
+ *                   log(max(Phi(-zm), 1e-12))           if x0 >  0.999
+ *                   log(max(Phi(a) - Phi(b), 1e-12))    otherwise, (a, b) = (zp, zm) if zm <= 0, (-zm, -zp) if not:
+ *                                                       the difference is taken where both values are small
+ * Per-sample outputs, [N] fp32 each: vb = mean(term)/ln 2, xstart_mse = mean(d*d), eps_mse = keps*mean(du*du),
+ * x0_sq = mean(x0*x0). At most DMC_VLB_MAX_BLOCKS blocks per sample leave partial sums in workspace
+ * (>= DMC_VLB_WORKSPACE_FLOATS(N) floats), added in block order: a fixed order, no atomics, deterministic.
+ * x_next != NULL: sample n with t_next[n] >= 0 gets x_next = sa[t_next]*x0 + s1[t_next]*z_next (sa, s1: [T];
+ * each op rounded once, no fma: the bits of dmc_q_sample); a sample with t_next[n] < 0 is not written. x_next == NULL:
+ * z_next, t_next, sa, s1 are unread. 16-byte accesses when per_sample % 4 == 0 and every pointer read or written is
+ * 16-byte aligned, element-wise otherwise. */
+int dmc_vlb_step(const float* x0, const float* x_t, const float* pred, const int64_t* t, const float* coef, int T,
+                 int clip, const float* z_next, const int64_t* t_next, const float* sa, const float* s1,
+                 int N, int per_sample, float* x_next, float* vb, float* xstart_mse, float* eps_mse,
+                 float* x0_sq, float* workspace, void* stream);
 
 /* DDIM.p_sample update (diffusion/ddim.py:154-208), fused; alpha gathers on device; if any
  * t_next < 0 the reference uses alpha_next = 1 for the whole batch (:176-179), so does this.
