@@ -20,6 +20,7 @@ LOSS = {"l1": 0, "l2": 1, "huber": 2}
 PRED = {"eps": 0, "v": 1}    # include/dmc.h DMC_PRED_*
 OBJECTIVE_MAX_BLOCKS = 64    # include/dmc.h DMC_OBJECTIVE_MAX_BLOCKS
 VLB_MAX_BLOCKS = 64          # include/dmc.h DMC_VLB_MAX_BLOCKS (DMC_VLB_WORKSPACE_FLOATS(N) = 4 * this * N)
+LVAR_COLS = 8                # include/dmc.h DMC_LVAR_COLS (DMC_HYBRID_WORKSPACE_FLOATS(N) = 2 * OBJECTIVE_MAX_BLOCKS * N)
 PACK_FWD, PACK_DGRAD, PACK_UPDGRAD, PACK_UPFOLD, PACK_DOWNDGRAD = 0, 1, 2, 3, 4
 FOLD_NONE, FOLD_UP, FOLD_DOWN_DGRAD = 0, 1, 2   # include/dmc.h DMC_FOLD_*
 FOLD_PACK = {FOLD_UP: PACK_UPFOLD, FOLD_DOWN_DGRAD: PACK_DOWNDGRAD}
@@ -178,6 +179,13 @@ def _load():
                                       _c_p, _c_p]),
         "dmc_vlb_step": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int,
                                   _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
+        "dmc_hybrid_objective": (_c_int, [_c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int,
+                                          _c_int, _c_int, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p]),
+        "dmc_vlb_step_learned": (_c_int, [_c_p, _c_p, _c_p, _c_long, _c_p, _c_long, _c_p, _c_p, _c_int, _c_int, _c_p,
+                                          _c_p, _c_p, _c_p, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
+                                          _c_p]),
+        "dmc_ddpm_step_learned": (_c_int, [_c_p, _c_p, _c_long, _c_p, _c_long, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
+                                           _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p]),
         "dmc_ddim_step": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_f, _c_int, _c_p, _c_p,
                                    _c_p]),
         "dmc_ddpm_step": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int,

@@ -214,14 +214,16 @@ __global__ void loss_bwd_kernel(int type, const float* pred, const float* target
 // weights (Hang et al. 2023, arXiv:2303.09556) come from the host as a [T] table (diffusion/_objective.py). One
 // element: target, the loss term of loss_partial_kernel and, when a gradient is asked for, loss_bwd_kernel's value;
 // every op is a separate rounding.
+DMC_DEV float obj_target(int pred_type, float sa, float s1, float x0, float e) {
+  if (pred_type != DMC_PRED_V) return e;
+  const float a_ = sa * e;
+  const float b_ = s1 * x0;
+  return a_ - b_;
+}
+
 DMC_DEV float obj_elem(int pred_type, int type, float sa, float s1, float p, float x0, float e, bool grad, float scale,
                        float& dp) {
-  float target = e;
-  if (pred_type == DMC_PRED_V) {
-    const float a_ = sa * e;
-    const float b_ = s1 * x0;
-    target = a_ - b_;
-  }
+  const float target = obj_target(pred_type, sa, s1, x0, e);
   if (grad) {
     const float d = p - target;
     float v;
@@ -370,17 +372,36 @@ struct VlbRow {
 // Exact normal CDF (not the tanh approximation of some public implementations).
 DMC_DEV float vlb_cdf(float z) { return 0.5f * erfcf(-z * 0.70710678118654752f); }
 
-// -log p of one element under the decoder's Gaussian discretised on the 8-bit grid k/127.5 - 1; d = x0 - mean
-DMC_DEV float vlb_decoder(float x0, float d, float isig) {
+DMC_DEV float vlb_zpdf(float z) { return z * (0.39894228040143268f * expf(-0.5f * z * z)); }   // z * phi(z)
+
+// -log p of one element under the decoder's Gaussian discretised on the 8-bit grid k/127.5 - 1; d = x0 - mean.
+// GRAD: dlv = d(-log p) / d(log variance), with isig = exp(-0.5 log variance): dz/dlv = -z/2 for both z, so
+// dlv = 0.5 (zp phi(zp) - zm phi(zm)) / p with the absent edge's term dropped, and 0 where the floor acts (as clamp
+// gives under autograd).
+template <bool GRAD>
+DMC_DEV float vlb_decoder_g(float x0, float d, float isig, float& dlv) {
   const float h = 1.0f / 255.0f;
   const float zp = (d + h) * isig;
   const float zm = (d - h) * isig;
-  float pr;
-  if (x0 < -0.999f) pr = vlb_cdf(zp);
-  else if (x0 > 0.999f) pr = vlb_cdf(-zm);
-  else if (zm <= 0.f) pr = vlb_cdf(zp) - vlb_cdf(zm);
-  else pr = vlb_cdf(-zm) - vlb_cdf(-zp);      // both values below 1/2: the difference keeps its digits
+  float pr, num = 0.f;
+  if (x0 < -0.999f) {
+    pr = vlb_cdf(zp);
+    if (GRAD) num = vlb_zpdf(zp);
+  } else if (x0 > 0.999f) {
+    pr = vlb_cdf(-zm);
+    if (GRAD) num = -vlb_zpdf(zm);
+  } else {
+    if (zm <= 0.f) pr = vlb_cdf(zp) - vlb_cdf(zm);
+    else pr = vlb_cdf(-zm) - vlb_cdf(-zp);      // both values below 1/2: the difference keeps its digits
+    if (GRAD) num = vlb_zpdf(zp) - vlb_zpdf(zm);
+  }
+  if (GRAD) dlv = pr >= 1e-12f ? 0.5f * num / pr : 0.f;
   return -logf(fmaxf(pr, 1e-12f));
+}
+
+DMC_DEV float vlb_decoder(float x0, float d, float isig) {
+  float unused;
+  return vlb_decoder_g<false>(x0, d, isig, unused);
 }
 
 struct VlbSums {
@@ -390,16 +411,21 @@ struct VlbSums {
 // u = c_x*x_t - c_p*pred is the x0 prediction as fp32 holds it. x0 - u is formed without u's rounding, as
 // (x0 - c_x*x_t) + c_p*pred plus the two products' rounding errors (exact, by fma): where the prediction is good the
 // difference is small against x0 and would otherwise keep only its leading digits.
-DMC_DEV void vlb_elem(const VlbRow& r, bool dec, int clip, float x0, float xt, float p, VlbSums& s) {
-  const float a_ = r.cx * xt;
-  const float ae = fmaf(r.cx, xt, -a_);
-  const float b_ = r.cp * p;
-  const float be = fmaf(r.cp, p, -b_);
+DMC_DEV void vlb_delta(float cx, float cp, int clip, float x0, float xt, float p, float& d, float& du) {
+  const float a_ = cx * xt;
+  const float ae = fmaf(cx, xt, -a_);
+  const float b_ = cp * p;
+  const float be = fmaf(cp, p, -b_);
   const float u = a_ - b_;
-  const float du = ((x0 - a_) + b_) + (be - ae);
-  float d = du;
+  du = ((x0 - a_) + b_) + (be - ae);
+  d = du;
   if (clip && u > 1.f) d = x0 - 1.f;
   if (clip && u < -1.f) d = x0 + 1.f;
+}
+
+DMC_DEV void vlb_elem(const VlbRow& r, bool dec, int clip, float x0, float xt, float p, VlbSums& s) {
+  float d, du;
+  vlb_delta(r.cx, r.cp, clip, x0, xt, p, d, du);
   const float d2 = d * d;
   s.term += dec ? vlb_decoder(x0, d, r.isig) : r.kvar + r.kprec * d2;
   s.dd += d2;
@@ -478,20 +504,326 @@ __global__ __launch_bounds__(256) void vlb_step_kernel(const float* x0, const fl
 }
 
 // Thread n adds sample n's partials in block order: a fixed order, no atomics.
+// keps is column keps_col of the table's cols-wide rows.
 __global__ __launch_bounds__(256) void vlb_final_kernel(const float* partial, int gx, const int64_t* t,
-                                                        const float* coef, int T, int N, int per, float* vb,
-                                                        float* xstart_mse, float* eps_mse, float* x0_sq) {
+                                                        const float* coef, int cols, int keps_col, int T, int N,
+                                                        int per, float* vb, float* xstart_mse, float* eps_mse,
+                                                        float* x0_sq) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
   float s[4] = {0.f, 0.f, 0.f, 0.f};
   for (int b = 0; b < gx; ++b)
     for (int k = 0; k < 4; ++k) s[k] += partial[((size_t)n * gx + b) * 4 + k];
-  const float keps = coef[clamp_t(t[n], T) * 6 + 4];
+  const float keps = coef[clamp_t(t[n], T) * cols + keps_col];
   const float fp = (float)per;
   vb[n] = (s[0] / fp) / 0.69314718055994531f;
   xstart_mse[n] = s[1] / fp;
   eps_mse[n] = keps * (s[2] / fp);
   x0_sq[n] = s[3] / fp;
+}
+
+// ---------------- learned variances: hybrid loss, bound step and sampler step ----------------
+// Nichol & Dhariwal 2021 (arXiv:2102.09672 §3.1, eq. 15-16): the network's second half v interpolates the log-variance
+// between the posterior's (lv_min) and beta's: lv_p = lv_min + d, d = (v + 1)/2 * R, R = lv_max - lv_min, not clamped.
+// The host table is diffusion/_vlb.py learned_coefficients: row {c_x, c_p, c1, lv_min, R, kmin, keps, lv_max}. With
+// delta = x0 - x0_pred (the means differ by c1*delta and are never formed) the KL against the true posterior is
+//   0.5 (d + expm1(-d)) + kmin exp(-d) delta^2,   kmin = 0.5 c1^2 exp(-lv_min)
+// in the expm1 form: R falls to 8e-7 at the noisy end, where -1 + d + exp(-d) is exactly 0 in fp32.
+struct LvarRow {
+  float lvmin, R, kmin;
+};
+
+DMC_DEV LvarRow lvar_row(const float* coef, long tt) {
+  const float* c = coef + tt * DMC_LVAR_COLS;
+  return LvarRow{c[3], c[4], c[5]};
+}
+
+DMC_DEV float lvar_d(const LvarRow& r, float v) {
+  const float frac = (v + 1.f) * 0.5f;
+  return frac * r.R;
+}
+
+// The term of one element (KL for t >= 1, the decoder's -log p for t = 0: dec), in nats; GRAD: dv = d term / d v.
+// The one function behind dmc_hybrid_objective, dmc_vlb_step_learned and (lvar_d) dmc_ddpm_step_learned.
+template <bool GRAD>
+DMC_DEV float lvar_term(const LvarRow& r, bool dec, float x0, float delta, float v, float& dv) {
+  const float d = lvar_d(r, v);
+  const float hr = 0.5f * r.R;                  // d lv_p / d v
+  if (dec) {
+    const float isig = expf(-0.5f * (r.lvmin + d));
+    float dlv = 0.f;
+    const float term = vlb_decoder_g<GRAD>(x0, delta, isig, dlv);
+    if (GRAD) dv = dlv * hr;
+    return term;
+  }
+  const float em = expm1f(-d);
+  const float q = (r.kmin * (1.f + em)) * (delta * delta);
+  if (GRAD) dv = (-0.5f * em - q) * hr;
+  return 0.5f * (d + em) + q;
+}
+
+// objective_kernel over out = [N][2][per]: the prediction half goes through obj_elem unchanged (so L_simple and its
+// gradient keep dmc_objective's bits), the v half gets the term with delta = c_p*(pred - target), which needs neither
+// x_t nor a division. The term sends no gradient to the prediction half. Block (bx, n) leaves {simple, term} sums at
+// partial[(n * gridDim.x + bx) * 2 ..]. x0 is read where the sample needs it: v-prediction, or t = 0 (the edges).
+template <bool VEC, bool GRAD>
+__global__ __launch_bounds__(256) void hybrid_objective_kernel(int pred_type, int type, const float* out,
+                                                               const float* x0, const float* noise, const int64_t* t,
+                                                               const float* sa, const float* s1, const float* w,
+                                                               const float* coef, int T, int N, int per,
+                                                               float vlb_weight, const float* dloss, float* dout,
+                                                               float* partial) {
+  __shared__ float red[2][4];
+  const bool isv = pred_type == DMC_PRED_V;
+  const float g = GRAD ? dloss[0] / (float)((long)N * per) : 0.f;
+  const float gv = (g * vlb_weight) / 0.69314718055994531f;
+  for (int n = blockIdx.y; n < N; n += gridDim.y) {
+    const long tt = clamp_t(t[n], T);
+    const float san = isv ? sa[tt] : 0.f, s1n = isv ? s1[tt] : 0.f;
+    const float cp = coef[tt * DMC_LVAR_COLS + 1];
+    const LvarRow r = lvar_row(coef, tt);
+    const bool dec = tt == 0, rdx = isv || dec;
+    float scale = g;
+    if (w) scale = g * w[tt];
+    const size_t xbase = (size_t)n * per, obase = 2 * xbase;
+    float ss = 0.f, sv = 0.f;
+    if (VEC) {
+      const int per4 = per / 4;
+      for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < per4; q += gridDim.x * blockDim.x) {
+        const size_t i = xbase + (size_t)q * 4, o = obase + (size_t)q * 4;
+        const v4f pv = *(const v4f*)(out + o);
+        const v4f vv = *(const v4f*)(out + o + per);
+        const v4f ev = *(const v4f*)(noise + i);
+        v4f xv = {0.f, 0.f, 0.f, 0.f}, dpv = xv, dvv = xv;
+        if (rdx) xv = *(const v4f*)(x0 + i);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          float dp = 0.f, dv = 0.f;
+          ss += obj_elem(pred_type, type, san, s1n, pv[k], xv[k], ev[k], GRAD, scale, dp);
+          const float delta = cp * (pv[k] - obj_target(pred_type, san, s1n, xv[k], ev[k]));
+          sv += lvar_term<GRAD>(r, dec, xv[k], delta, vv[k], dv);
+          dpv[k] = dp;
+          dvv[k] = gv * dv;
+        }
+        if (GRAD) {
+          *(v4f*)(dout + o) = dpv;
+          *(v4f*)(dout + o + per) = dvv;
+        }
+      }
+    } else {
+      for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < per; q += gridDim.x * blockDim.x) {
+        const size_t i = xbase + q, o = obase + q;
+        const float p = out[o], xx = rdx ? x0[i] : 0.f, e = noise[i];
+        float dp = 0.f, dv = 0.f;
+        ss += obj_elem(pred_type, type, san, s1n, p, xx, e, GRAD, scale, dp);
+        const float delta = cp * (p - obj_target(pred_type, san, s1n, xx, e));
+        sv += lvar_term<GRAD>(r, dec, xx, delta, out[o + per], dv);
+        if (GRAD) {
+          dout[o] = dp;
+          dout[o + per] = gv * dv;
+        }
+      }
+    }
+    ss = wave_sum(ss);
+    sv = wave_sum(sv);
+    if ((threadIdx.x & 63) == 0) {
+      red[0][threadIdx.x >> 6] = ss;
+      red[1][threadIdx.x >> 6] = sv;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+      const float* rk = red[threadIdx.x];
+      partial[((size_t)n * gridDim.x + blockIdx.x) * 2 + threadIdx.x] = (rk[0] + rk[1]) + (rk[2] + rk[3]);
+    }
+    __syncthreads();   // red is reused by the block's next sample
+  }
+}
+
+// objective_final_kernel's order for both sums: loss = {simple + vlb, simple, vlb}, simple as dmc_objective's loss[0],
+// vlb = vlb_weight * (1/N) sum_n (1/per) * (sample n's term partials in block order) / ln 2.
+__global__ __launch_bounds__(256) void hybrid_final_kernel(const float* partial, int gx, const int64_t* t,
+                                                           const float* w, int T, int N, int per, float vlb_weight,
+                                                           float* loss) {
+  __shared__ float sm[2][256];
+  float total = 0.f, totalv = 0.f;
+  for (int n0 = 0; n0 < N; n0 += 256) {
+    const int n = n0 + threadIdx.x;
+    float m = 0.f, mv = 0.f;
+    if (n < N) {
+      float s = 0.f, sv = 0.f;
+      for (int b = 0; b < gx; ++b) {
+        s += partial[((size_t)n * gx + b) * 2];
+        sv += partial[((size_t)n * gx + b) * 2 + 1];
+      }
+      m = s / (float)per;
+      if (w) m = w[clamp_t(t[n], T)] * m;
+      mv = (sv / (float)per) / 0.69314718055994531f;
+    }
+    sm[0][threadIdx.x] = m;
+    sm[1][threadIdx.x] = mv;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const int cnt = N - n0 < 256 ? N - n0 : 256;
+      for (int k = 0; k < cnt; ++k) {
+        total += sm[0][k];
+        totalv += sm[1][k];
+      }
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float simple = total / (float)N;
+    const float vlb = vlb_weight * (totalv / (float)N);
+    loss[0] = simple + vlb;
+    loss[1] = simple;
+    loss[2] = vlb;
+  }
+}
+
+// vlb_step_kernel with the learned term: pred and v are rows of the model's [N][2][per] output, read in place through
+// their row strides.
+template <bool VEC>
+__global__ __launch_bounds__(256) void vlb_step_learned_kernel(const float* x0, const float* xt, const float* pred,
+                                                               long pred_ld, const float* v, long v_ld,
+                                                               const int64_t* t, const float* coef, int T, int clip,
+                                                               const float* zn, const int64_t* t_next,
+                                                               const float* sa, const float* s1, int N, int per,
+                                                               float* x_next, float* partial) {
+  __shared__ float red[4][4];
+  for (int n = blockIdx.y; n < N; n += gridDim.y) {
+    const long tt = clamp_t(t[n], T);
+    const float cx = coef[tt * DMC_LVAR_COLS], cp = coef[tt * DMC_LVAR_COLS + 1];
+    const LvarRow r = lvar_row(coef, tt);
+    const bool dec = tt == 0;
+    bool fwd = false;
+    float an = 0.f, bn = 0.f;
+    if (x_next != nullptr && t_next[n] >= 0) {
+      const long tn = clamp_t(t_next[n], T);
+      fwd = true;
+      an = sa[tn];
+      bn = s1[tn];
+    }
+    const size_t base = (size_t)n * per;
+    const float* pn = pred + (size_t)n * pred_ld;
+    const float* vn = v + (size_t)n * v_ld;
+    VlbSums s{0.f, 0.f, 0.f, 0.f};
+    float unused;
+    if (VEC) {
+      const int per4 = per / 4;
+      for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < per4; q += gridDim.x * blockDim.x) {
+        const size_t i = base + (size_t)q * 4;
+        const v4f xv = *(const v4f*)(x0 + i);
+        const v4f tv = *(const v4f*)(xt + i);
+        const v4f pv = *(const v4f*)(pn + (size_t)q * 4);
+        const v4f vv = *(const v4f*)(vn + (size_t)q * 4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          float d, du;
+          vlb_delta(cx, cp, clip, xv[k], tv[k], pv[k], d, du);
+          s.term += lvar_term<false>(r, dec, xv[k], d, vv[k], unused);
+          s.dd += d * d;
+          s.du += du * du;
+          s.xx += xv[k] * xv[k];
+        }
+        if (fwd) {
+          const v4f zv = *(const v4f*)(zn + i);
+          v4f ov;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const float u = an * xv[k];
+            const float w_ = bn * zv[k];
+            ov[k] = u + w_;
+          }
+          *(v4f*)(x_next + i) = ov;
+        }
+      }
+    } else {
+      for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < per; q += gridDim.x * blockDim.x) {
+        const size_t i = base + q;
+        const float xx = x0[i];
+        float d, du;
+        vlb_delta(cx, cp, clip, xx, xt[i], pn[q], d, du);
+        s.term += lvar_term<false>(r, dec, xx, d, vn[q], unused);
+        s.dd += d * d;
+        s.du += du * du;
+        s.xx += xx * xx;
+        if (fwd) {
+          const float u = an * xx;
+          const float w_ = bn * zn[i];
+          x_next[i] = u + w_;
+        }
+      }
+    }
+    float sums[4] = {wave_sum(s.term), wave_sum(s.dd), wave_sum(s.du), wave_sum(s.xx)};
+    if ((threadIdx.x & 63) == 0)
+      for (int k = 0; k < 4; ++k) red[k][threadIdx.x >> 6] = sums[k];
+    __syncthreads();
+    if (threadIdx.x < 4) {
+      const float* rk = red[threadIdx.x];
+      partial[((size_t)n * gridDim.x + blockIdx.x) * 4 + threadIdx.x] = (rk[0] + rk[1]) + (rk[2] + rk[3]);
+    }
+    __syncthreads();   // red is reused by the block's next sample
+  }
+}
+
+// ddpm_step_kernel's ops with the learned standard deviation exp(0.5 (lv_min + d)); eps and v are rows of the model
+// output read in place. Grid as dpm_step_kernel: t and the table entries are block-uniform.
+DMC_DEV float ddpm_learned_elem(float a, float b, float k1, float k2, int clip, bool from_eps, float x, float e,
+                                float x0, bool nz, const LvarRow& r, float v, float z) {
+  if (from_eps) {
+    const float u = a * x;
+    const float w_ = b * e;
+    x0 = u - w_;
+  }
+  if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+  const float m1 = k1 * x0;
+  const float m2 = k2 * x;
+  const float mean = m1 + m2;
+  if (!nz) return mean;
+  const float sd = expf(0.5f * (r.lvmin + lvar_d(r, v)));
+  return mean + sd * z;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void ddpm_step_learned_kernel(const float* x, const float* eps, long eps_ld,
+                                                                const float* v, long v_ld, const float* x0_in,
+                                                                const int64_t* t, const float* sra, const float* srm1,
+                                                                const float* c1, const float* c2, const float* coef,
+                                                                int T, int N, int per, int clip, const float* z,
+                                                                float* out) {
+  const bool from_eps = x0_in == nullptr;
+  for (int n = blockIdx.y; n < N; n += gridDim.y) {
+    const long tt = clamp_t(t[n], T);
+    const float a = from_eps ? sra[tt] : 0.f, b = from_eps ? srm1[tt] : 0.f, k1 = c1[tt], k2 = c2[tt];
+    const LvarRow r = lvar_row(coef, tt);
+    const bool nz = z != nullptr && tt != 0;
+    const size_t base = (size_t)n * per;
+    const float* en = from_eps ? eps + (size_t)n * eps_ld : nullptr;
+    const float* vn = nz ? v + (size_t)n * v_ld : nullptr;
+    if (VEC) {
+      const int per4 = per / 4;
+      for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < per4; q += gridDim.x * blockDim.x) {
+        const size_t i = base + (size_t)q * 4;
+        const v4f zero = {0.f, 0.f, 0.f, 0.f};
+        const v4f xv = *(const v4f*)(x + i);
+        const v4f ev = from_eps ? *(const v4f*)(en + (size_t)q * 4) : zero;
+        const v4f x0v = from_eps ? zero : *(const v4f*)(x0_in + i);
+        const v4f vv = nz ? *(const v4f*)(vn + (size_t)q * 4) : zero;
+        const v4f zv = nz ? *(const v4f*)(z + i) : zero;
+        v4f ov;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          ov[k] = ddpm_learned_elem(a, b, k1, k2, clip, from_eps, xv[k], ev[k], x0v[k], nz, r, vv[k], zv[k]);
+        *(v4f*)(out + i) = ov;
+      }
+    } else {
+      for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < per; q += gridDim.x * blockDim.x) {
+        const size_t i = base + q;
+        out[i] = ddpm_learned_elem(a, b, k1, k2, clip, from_eps, x[i], from_eps ? en[q] : 0.f,
+                                   from_eps ? 0.f : x0_in[i], nz, r, nz ? vn[q] : 0.f, nz ? z[i] : 0.f);
+      }
+    }
+  }
 }
 
 // ---------------- samplers ----------------
@@ -1100,8 +1432,91 @@ extern "C" int dmc_vlb_step(const float* x0, const float* x_t, const float* pred
   else
     vlb_step_kernel<false><<<grid, 256, 0, s>>>(x0, x_t, pred, t, coef, T, clip, z_next, t_next, sa, s1, N, per, x_next,
                                                 ws);
-  vlb_final_kernel<<<(N + 255) / 256, 256, 0, s>>>(ws, (int)grid.x, t, coef, T, N, per, vb, xstart_mse, eps_mse, x0_sq);
+  vlb_final_kernel<<<(N + 255) / 256, 256, 0, s>>>(ws, (int)grid.x, t, coef, 6, 4, T, N, per, vb, xstart_mse, eps_mse,
+                                                   x0_sq);
   return dmc::check_launch("dmc_vlb_step");
+}
+
+extern "C" int dmc_hybrid_objective(int pred_type, int type, const float* out, const float* x0, const float* noise,
+                                    const int64_t* t, const float* sa, const float* s1, const float* w,
+                                    const float* coef, int T, int N, int per, float vlb_weight, const float* dloss,
+                                    float* loss, float* dout, float* ws, void* stream) {
+  DMC_REQUIRE(pred_type == DMC_PRED_EPS || pred_type == DMC_PRED_V, "hybrid_objective: prediction type %d", pred_type);
+  DMC_REQUIRE(type >= 0 && type <= 2, "hybrid_objective: loss type %d", type);
+  DMC_REQUIRE(T > 0 && N > 0 && per > 0, "hybrid_objective: T %d, N %d, per_sample %d must be positive", T, N, per);
+  DMC_REQUIRE(out && x0 && noise && t && coef && loss && ws,
+              "hybrid_objective: out, x0, noise, t, coef, loss and workspace must not be NULL");
+  DMC_REQUIRE(pred_type == DMC_PRED_EPS || (sa && s1), "hybrid_objective: v-prediction needs both tables");
+  DMC_REQUIRE(!dout || dloss, "hybrid_objective: dout needs the upstream gradient dloss");
+  const uintptr_t bits = (uintptr_t)out | (uintptr_t)x0 | (uintptr_t)noise | (uintptr_t)dout;
+  const bool vec = per % 4 == 0 && (bits & 15) == 0;   // then the v halves, per floats further on, are aligned too
+  const dim3 grid = sample_grid(vec ? per / 4 : per, N, DMC_OBJECTIVE_MAX_BLOCKS);
+  hipStream_t s = dmc::as_stream(stream);
+#define DMC_HYBRID_LAUNCH(VEC, GRAD)                                                                                  \
+  hybrid_objective_kernel<VEC, GRAD><<<grid, 256, 0, s>>>(pred_type, type, out, x0, noise, t, sa, s1, w, coef, T, N,  \
+                                                          per, vlb_weight, dloss, dout, ws)
+  if (vec && dout) DMC_HYBRID_LAUNCH(true, true);
+  else if (vec) DMC_HYBRID_LAUNCH(true, false);
+  else if (dout) DMC_HYBRID_LAUNCH(false, true);
+  else DMC_HYBRID_LAUNCH(false, false);
+#undef DMC_HYBRID_LAUNCH
+  hybrid_final_kernel<<<1, 256, 0, s>>>(ws, (int)grid.x, t, w, T, N, per, vlb_weight, loss);
+  return dmc::check_launch("dmc_hybrid_objective");
+}
+
+extern "C" int dmc_vlb_step_learned(const float* x0, const float* x_t, const float* pred, long pred_stride,
+                                    const float* v, long v_stride, const int64_t* t, const float* coef, int T,
+                                    int clip, const float* z_next, const int64_t* t_next, const float* sa,
+                                    const float* s1, int N, int per, float* x_next, float* vb, float* xstart_mse,
+                                    float* eps_mse, float* x0_sq, float* ws, void* stream) {
+  DMC_REQUIRE(T > 0 && N > 0 && per > 0, "vlb_step_learned: T %d, N %d, per_sample %d must be positive", T, N, per);
+  DMC_REQUIRE(x0 && x_t && pred && v && t && coef && vb && xstart_mse && eps_mse && x0_sq && ws,
+              "vlb_step_learned: only x_next and its operands z_next, t_next, sa, s1 may be NULL");
+  DMC_REQUIRE(pred_stride >= per && v_stride >= per, "vlb_step_learned: row strides %ld, %ld below per_sample %d",
+              pred_stride, v_stride, per);
+  DMC_REQUIRE(!x_next || (z_next && t_next && sa && s1),
+              "vlb_step_learned: x_next needs z_next, t_next and both tables");
+  const uintptr_t bits = (uintptr_t)x0 | (uintptr_t)x_t | (uintptr_t)pred | (uintptr_t)v | (uintptr_t)x_next |
+                         (x_next ? (uintptr_t)z_next : 0);   // a NULL or unread operand adds no bits
+  const bool vec = per % 4 == 0 && pred_stride % 4 == 0 && v_stride % 4 == 0 && (bits & 15) == 0;
+  const dim3 grid = sample_grid(vec ? per / 4 : per, N, DMC_VLB_MAX_BLOCKS);
+  hipStream_t s = dmc::as_stream(stream);
+  if (vec)
+    vlb_step_learned_kernel<true><<<grid, 256, 0, s>>>(x0, x_t, pred, pred_stride, v, v_stride, t, coef, T, clip, z_next,
+                                                       t_next, sa, s1, N, per, x_next, ws);
+  else
+    vlb_step_learned_kernel<false><<<grid, 256, 0, s>>>(x0, x_t, pred, pred_stride, v, v_stride, t, coef, T, clip,
+                                                        z_next, t_next, sa, s1, N, per, x_next, ws);
+  vlb_final_kernel<<<(N + 255) / 256, 256, 0, s>>>(ws, (int)grid.x, t, coef, DMC_LVAR_COLS, 6, T, N, per, vb,
+                                                   xstart_mse, eps_mse, x0_sq);
+  return dmc::check_launch("dmc_vlb_step_learned");
+}
+
+extern "C" int dmc_ddpm_step_learned(const float* x, const float* eps, long eps_stride, const float* v, long v_stride,
+                                     const float* x0_in, const int64_t* t, const float* sra, const float* srm1,
+                                     const float* c1, const float* c2, const float* coef, int T, int N, int per,
+                                     int clip, const float* z, float* out, void* stream) {
+  DMC_REQUIRE(T > 0 && N > 0 && per > 0, "ddpm_step_learned: T %d, N %d, per_sample %d must be positive", T, N, per);
+  DMC_REQUIRE(x && (eps || x0_in) && t && c1 && c2 && coef && out,
+              "ddpm_step_learned: x, eps (or x0_in), t, the tables and out must not be NULL");
+  DMC_REQUIRE(x0_in || (sra && srm1), "ddpm_step_learned: an eps input needs the sqrt_recip tables");
+  DMC_REQUIRE(!z || v, "ddpm_step_learned: z needs v");
+  DMC_REQUIRE((x0_in || eps_stride >= per) && (!z || v_stride >= per),
+              "ddpm_step_learned: row strides %ld, %ld below per_sample %d", eps_stride, v_stride, per);
+  const bool rd_eps = x0_in == nullptr, rd_v = z != nullptr;
+  const uintptr_t bits = (uintptr_t)x | (uintptr_t)out | (uintptr_t)x0_in | (uintptr_t)z |
+                         (rd_eps ? (uintptr_t)eps : 0) | (rd_v ? (uintptr_t)v : 0);   // unread operands add no bits
+  const bool vec = per % 4 == 0 && (bits & 15) == 0 && (!rd_eps || eps_stride % 4 == 0) &&
+                   (!rd_v || v_stride % 4 == 0);
+  const dim3 grid = sample_grid(vec ? per / 4 : per, N, 8192);
+  hipStream_t s = dmc::as_stream(stream);
+  if (vec)
+    ddpm_step_learned_kernel<true><<<grid, 256, 0, s>>>(x, eps, eps_stride, v, v_stride, x0_in, t, sra, srm1, c1, c2,
+                                                        coef, T, N, per, clip, z, out);
+  else
+    ddpm_step_learned_kernel<false><<<grid, 256, 0, s>>>(x, eps, eps_stride, v, v_stride, x0_in, t, sra, srm1, c1, c2,
+                                                         coef, T, N, per, clip, z, out);
+  return dmc::check_launch("dmc_ddpm_step_learned");
 }
 
 extern "C" int dmc_ddim_step(const float* x, const float* eps, const float* x0_in, const int64_t* t, const int64_t* t_next,

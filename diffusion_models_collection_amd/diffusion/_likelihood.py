@@ -17,13 +17,14 @@ from ._graph import StepGraph, cache_for, run_loop
 
 
 class LikelihoodMixin:
-    """Needs the sampler's alphas_cumprod, num_timesteps, prediction_type, q_sample and _tab."""
+    """Needs the sampler's alphas_cumprod, num_timesteps, prediction_type, q_sample and _tab (and, for
+    variance='learned', ObjectiveMixin's variance_type, _lvar_table, _check_out and _pred_of)."""
 
     def _vlb_table(self, variance, dev):
         """[T, 6] fp32 device table of _vlb.vlb_coefficients, built and uploaded once per (prediction type,
         variance)."""
         if variance not in _vlb.VARIANCES:
-            raise ValueError(f"Unknown variance: {variance!r} (expected one of {_vlb.VARIANCES})")
+            raise ValueError(f"Unknown variance: {variance!r} (expected one of {_vlb.VARIANCES + ('learned',)})")
         key = (self.prediction_type, variance)
         cache = self.__dict__.setdefault("_vlb_tables", {})
         c = cache.get(key)
@@ -36,11 +37,18 @@ class LikelihoodMixin:
     def calc_bpd(self, model, x0, y=None, clip_denoised=True, variance='fixed_small', noise=None, timesteps=None):
         """The variational bound on -log2 p(x0) per dimension, term by term. x0: [B, ...] in [-1, 1] on the 8-bit grid
         k/127.5 - 1. Walks t = T-1 .. 0, or the given `timesteps` (distinct ints in [0, T), taken in descending
-        order). variance: the model's fixed variance, 'fixed_small' (posterior variance) or 'fixed_large' (beta).
+        order). variance: the model's fixed variance, 'fixed_small' (posterior variance) or 'fixed_large' (beta), or
+        'learned' (a variance_type='learned_range' sampler only: the model's own, dmc_vlb_step_learned reading both
+        halves of the output in place; on such a sampler the two fixed choices use the prediction half, so the three
+        can be compared on one model).
         noise: None (torch.randn_like per step), a [T, B, ...] tensor indexed by t, or a callable t -> tensor: the draw
         that makes x_t. y gives the conditional bound (there is no guided variant: a guided score is no likelihood).
         Returns fp32 device tensors: vb, xstart_mse, eps_mse [B, S] (columns in the order walked), timesteps [S]
         (int64), prior_bpd [B], and total_bpd [B] = vb.sum(1) + prior_bpd when all T steps were walked, else None."""
+        learned = variance == "learned"
+        lr = getattr(self, "variance_type", "fixed") == "learned_range"
+        if learned and not lr:
+            raise ValueError("variance='learned' needs a sampler with variance_type='learned_range'")
         if not torch.is_tensor(x0) or x0.dim() < 2:
             raise ValueError("x0 must be a [B, ...] tensor")
         if not x0.is_cuda or (y is not None and not y.is_cuda):
@@ -52,7 +60,7 @@ class LikelihoodMixin:
         x0 = x0.float().contiguous()
         dev, B, shape = x0.device, x0.shape[0], x0.shape
         S, n = len(ts), x0.numel()
-        coef = self._vlb_table(variance, dev)
+        coef = self._lvar_table(dev) if learned else self._vlb_table(variance, dev)
         sa, s1 = self._tab("sqrt_alphas_cumprod", dev), self._tab("sqrt_one_minus_alphas_cumprod", dev)
         clip = bool(clip_denoised)
         has_y = y is not None
@@ -83,9 +91,15 @@ class LikelihoodMixin:
 
         def fn(s, t, tn, z, x0_, yy=None):
             x = s[:n].view(shape)
-            pred = model(x, t, yy).contiguous().float()
+            pred = model(x, t, yy)
             new = torch.empty_like(s)
             out = new[n:].view(4, B)
+            if learned:
+                K.vlb_step_learned(x0_, x, self._check_out(pred, x).contiguous().float(), t, coef, clip=clip, z_next=z,
+                                   t_next=tn, sa=sa, s1=s1, x_next=new[:n].view(shape),
+                                   rows=(out[0], out[1], out[2], out[3]))
+                return new
+            pred = (self._pred_of(pred, x) if lr else pred).contiguous().float()
             K.vlb_step(x0_, x, pred, t, coef, clip=clip, z_next=z, t_next=tn, sa=sa, s1=s1, x_next=new[:n].view(shape),
                        out=(out[0], out[1], out[2], out[3]))
             return new
@@ -96,7 +110,7 @@ class LikelihoodMixin:
             bar.update(1)
             rows[i].copy_(s[n:].view(4, B))
 
-        key = ("bpd", self.prediction_type, variance, clip, has_y, tuple(shape), coef.data_ptr(),
+        key = ("bpd", self.prediction_type, getattr(self, "variance_type", "fixed"), variance, clip, has_y, tuple(shape), coef.data_ptr(),
                self.alphas_cumprod.data_ptr())
         run_loop(st, S, inputs, fn, StepGraph.eligible(model, x0, True, False), record,
                  cache=cache_for(model, key, self, st), const=(4, 5) if has_y else (4,))

@@ -23,7 +23,7 @@ import torch
 from tqdm import tqdm
 
 from .. import kernels as K
-from . import _objective, _schedule
+from . import _objective, _schedule, _vlb
 from ._edit_loop import EditMixin
 from ._graph import StepGraph, cache_for, run_loop
 from ._likelihood import LikelihoodMixin
@@ -34,8 +34,9 @@ class DDIM(ObjectiveMixin, EditMixin, LikelihoodMixin):
     """DDIM diffusion process with accelerated sampling (diffusion/ddim.py:13-351)."""
 
     def __init__(self, num_timesteps=1000, num_inference_steps=50, beta_start=0.0001, beta_end=0.02,
-                 beta_schedule='linear', eta=0.0, device='cuda', prediction_type='eps'):
+                 beta_schedule='linear', eta=0.0, device='cuda', prediction_type='eps', variance_type='fixed'):
         self.prediction_type = _objective.check_prediction_type(prediction_type)
+        self.variance_type = _vlb.check_variance_type(variance_type)
         self.num_timesteps = num_timesteps
         self.num_inference_steps = num_inference_steps
         self.eta = eta
@@ -67,15 +68,14 @@ class DDIM(ObjectiveMixin, EditMixin, LikelihoodMixin):
         return K.q_sample(x_start.float(), noise.float(), t.to(dev).long().contiguous(),
                           self._tab("sqrt_alphas_cumprod", dev), self._tab("sqrt_one_minus_alphas_cumprod", dev))
 
-    def p_losses(self, model, x_start, t, y=None, noise=None, loss_type='l2', snr_gamma=None):
-        """As DDPM.p_losses (snr_gamma and the v target are not in the reference)."""
+    def p_losses(self, model, x_start, t, y=None, noise=None, loss_type='l2', snr_gamma=None, vlb_weight=None,
+                 return_parts=False):
+        """As DDPM.p_losses (snr_gamma, the v target and the hybrid loss of learned_range are not in the reference)."""
         if noise is None:
             noise = torch.randn_like(x_start)
         x_noisy = self.q_sample(x_start, t, noise)
         predicted_noise = model(x_noisy, t, y)
-        if self._default_objective(snr_gamma):
-            return diffusion_loss(predicted_noise, noise, loss_type)
-        return self._objective_loss(predicted_noise, x_start, noise, t, loss_type, snr_gamma)
+        return self._losses(predicted_noise, x_start, noise, t, loss_type, snr_gamma, vlb_weight, return_parts)
 
     def _extract(self, a, t, x_shape):
         batch_size = t.shape[0]
@@ -85,9 +85,10 @@ class DDIM(ObjectiveMixin, EditMixin, LikelihoodMixin):
 
     @torch.no_grad()
     def p_sample(self, model, x, t, t_next, y=None, clip_denoised=True, eps=None, x0_pred=None, noise=None):
-        """x_t -> x_{t_next} (diffusion/ddim.py:154-208), one fused kernel after the model call."""
+        """x_t -> x_{t_next} (diffusion/ddim.py:154-208), one fused kernel after the model call. With learned_range
+        the update keeps DDIM's own sigma: the prediction half is taken (one contiguous copy per step), v is ignored."""
         if eps is None:
-            eps = model(x, t, y)
+            eps = self._pred_of(model(x, t, y), x)
             if self.prediction_type == "v":
                 eps, x0_pred = self._convert(eps, x, t)
         _require_cuda(x, eps)
@@ -122,7 +123,7 @@ class DDIM(ObjectiveMixin, EditMixin, LikelihoodMixin):
 
     def _step_plain(self, model, x, t, tn, y, z, shared_t, clip=True):
         """One step of sample(): shared with img2img / inpaint / invert."""
-        eps, x0 = (model(x, t[:1], None) if shared_t else None), None
+        eps, x0 = (self._pred_of(model(x, t[:1], None), x) if shared_t else None), None
         if eps is not None and self.prediction_type == "v":
             eps, x0 = self._convert(eps, x, t)
         return self.p_sample(model, x, t, tn, y, clip_denoised=clip, eps=eps, x0_pred=x0, noise=z)
@@ -148,7 +149,7 @@ class DDIM(ObjectiveMixin, EditMixin, LikelihoodMixin):
                 return self._step_plain(model, x, args[0], args[1], yy, z, shared_t)
             return self._step_cfg(model, x, args[0], args[1], yy, z, cfg_scale, p_threshold)
 
-        key = ("ddim", self.prediction_type, self.eta, shared_t, y is not None, cfg_scale, p_threshold,
+        key = ("ddim", self.prediction_type, self.variance_type, self.eta, shared_t, y is not None, cfg_scale, p_threshold,
                self.alphas_cumprod.data_ptr())
         return (self.inference_timesteps[i0:].cpu().numpy(), (lambda j: (tab[j], tab[j + 1])), step, self.eta > 0,
                 key)
@@ -175,7 +176,7 @@ class DDIM(ObjectiveMixin, EditMixin, LikelihoodMixin):
         def fn(xx, t, tn, yy=None):
             return self._step_plain(model, xx, t, tn, yy, None, shared_t, clip=False)
 
-        key = ("ddim_invert", self.prediction_type, shared_t, has_y, self.alphas_cumprod.data_ptr())
+        key = ("ddim_invert", self.prediction_type, self.variance_type, shared_t, has_y, self.alphas_cumprod.data_ptr())
         return self._edit_run(model, x, up.shape[0] - 1, inputs, fn, key, (3,) if has_y else (),
                               return_all_timesteps, "DDIM inversion")
 
@@ -215,7 +216,7 @@ class DDIM(ObjectiveMixin, EditMixin, LikelihoodMixin):
                 imgs.append(x.cpu())
 
         cache = None if return_all_timesteps else cache_for(
-            model, ("ddim", self.prediction_type, self.eta, shared_t, has_y, has_z, clip,
+            model, ("ddim", self.prediction_type, self.variance_type, self.eta, shared_t, has_y, has_z, clip,
                     self.alphas_cumprod.data_ptr()),
             self, img)
         img = run_loop(img, S, inputs, fn, StepGraph.eligible(model, img, True, False),
@@ -259,7 +260,7 @@ class DDIM(ObjectiveMixin, EditMixin, LikelihoodMixin):
                 imgs.append(x.cpu())
 
         cache = None if return_all_timesteps else cache_for(
-            model, ("ddim_cfg", self.prediction_type, self.eta, has_z, float(cfg_scale), p_threshold, ac.data_ptr()),
+            model, ("ddim_cfg", self.prediction_type, self.variance_type, self.eta, has_z, float(cfg_scale), p_threshold, ac.data_ptr()),
             self, img)
         img = run_loop(img, S, inputs, fn, StepGraph.eligible(model, img, True, False),
                        record, cache=cache, const=(3,))

@@ -22,6 +22,12 @@ weights each sample by min-SNR-gamma (arXiv:2303.09556); see _objective.py. With
 anything new. img2img / inpaint (not in the reference either; _edit_loop.EditMixin, _edit.py, dmc_known_blend) run the
 steps of sample / sample_with_cfg from, or around, a given image. calc_bpd (not in the reference; _likelihood.LikelihoodMixin,
 _vlb.py, dmc_vlb_step) evaluates the variational bound in bits per dimension.
+DDPM(variance_type='learned_range') (not in the reference; arXiv:2102.09672 §3.1) takes a model that returns 2C channels,
+the prediction and the log-variance interpolation v:
+  hybrid loss         -> dmc_hybrid_objective (L_simple + vlb_weight * L_vlb, both halves' gradient, one pass), via _HybridFn
+  p_sample / mean     -> dmc_ddpm_step_learned (both halves of the model output read in place, the model's own sigma)
+  calc_bpd 'learned'  -> dmc_vlb_step_learned
+With the default 'fixed' nothing new is launched.
 """
 import numpy as np
 import torch
@@ -29,7 +35,7 @@ import torch.nn.functional as F
 from tqdm import tqdm
 
 from .. import kernels as K
-from . import _objective, _schedule
+from . import _objective, _schedule, _vlb
 from ._edit_loop import EditMixin
 from ._graph import StepGraph, run_loop
 from ._likelihood import LikelihoodMixin
@@ -90,16 +96,98 @@ class _ObjectiveFn(torch.autograd.Function):
         return (dpred,) + (None,) * 8
 
 
+class _HybridFn(torch.autograd.Function):
+    """L_hybrid of a network with a variance head (dmc_hybrid_objective), in the shape of _ObjectiveFn: the forward is the
+    kernel without a gradient output, the backward the same kernel with the upstream scalar. Returns (total, simple,
+    vlb); only the total carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, out, x0, noise, t, sa, s1, w, coef, pred_type, loss_type, vlb_weight):
+        out = out.contiguous().float()
+        ctx.save_for_backward(out, x0, noise, t, sa, s1, w, coef)
+        ctx.args = (pred_type, loss_type, vlb_weight)
+        loss = K.hybrid_objective(pred_type, loss_type, out, x0, noise, t, sa, s1, coef, w, vlb_weight, grad=False)[0]
+        total, simple, vlb = loss[0], loss[1], loss[2]
+        ctx.mark_non_differentiable(simple, vlb)
+        return total, simple, vlb
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        out, x0, noise, t, sa, s1, w, coef = ctx.saved_tensors
+        pred_type, loss_type, vlb_weight = ctx.args
+        _, dout = K.hybrid_objective(pred_type, loss_type, out, x0, noise, t, sa, s1, coef, w, vlb_weight,
+                                     dloss=g.contiguous().float())
+        return (dout,) + (None,) * 10
+
+
 class ObjectiveMixin:
-    """prediction_type, the min-SNR weight tables and the two launches they need, shared by DDPM and DDIM (and so
-    DPMSolver): both carry sqrt_alphas_cumprod / sqrt_one_minus_alphas_cumprod and _tab()."""
+    """prediction_type, variance_type, the min-SNR weight tables and the launches they need, shared by DDPM and DDIM
+    (and so DPMSolver): both carry sqrt_alphas_cumprod / sqrt_one_minus_alphas_cumprod and _tab()."""
 
     prediction_type = "eps"
+    variance_type = "fixed"
 
     def set_prediction_type(self, prediction_type):
         """'eps' or 'v'. Drops the sampler's cached step graphs (their steps were captured for the old type)."""
         self.prediction_type = _objective.check_prediction_type(prediction_type)
         self.__dict__.pop("_step_graphs", None)
+
+    def set_variance_type(self, variance_type):
+        """'fixed', or 'learned_range': the model returns 2C channels, the prediction and the variance interpolation v
+        (arXiv:2102.09672 §3.1). Drops the sampler's cached step graphs, as set_prediction_type does."""
+        self.variance_type = _vlb.check_variance_type(variance_type)
+        self.__dict__.pop("_step_graphs", None)
+
+    def _lvar_table(self, dev):
+        """[T, 8] fp32 device table of _vlb.learned_coefficients, built and uploaded once per prediction type."""
+        cache = self.__dict__.setdefault("_lvar_tables", {})
+        c = cache.get(self.prediction_type)
+        if c is None or c.device != dev:
+            c = cache[self.prediction_type] = torch.from_numpy(
+                _vlb.learned_coefficients(self.alphas_cumprod.cpu().numpy(), self.prediction_type)).to(dev)
+        return c
+
+    @staticmethod
+    def _vlb_weight(vlb_weight):
+        w = 0.001 if vlb_weight is None else vlb_weight      # the paper's lambda
+        if isinstance(w, (bool, str)) or not isinstance(w, (int, float)) or not 0.0 <= float(w) < float("inf"):
+            raise ValueError(f"vlb_weight must be a finite number >= 0, got {vlb_weight!r}")
+        return float(w)
+
+    def _check_out(self, out, x):
+        """A learned_range model returns [B', 2C, ...] for x = [B, C, ...] (B' = 2B under CFG)."""
+        if out.dim() != x.dim() or out.shape[1] != 2 * x.shape[1] or out.shape[2:] != x.shape[2:]:
+            raise ValueError(f"variance_type='learned_range' needs a model output with {2 * x.shape[1]} channels "
+                             f"(prediction, then v), got {tuple(out.shape)} for an input {tuple(x.shape)}")
+        return out
+
+    def _pred_of(self, out, x):
+        """The prediction of a model output: the output itself, or for learned_range its first C channels as ONE
+        contiguous copy (the samplers with a sigma of their own, DDIM and DPM-Solver, ignore v)."""
+        if self.variance_type != "learned_range":
+            return out
+        return self._check_out(out, x)[:, :x.shape[1]].contiguous()
+
+    def _losses(self, out, x_start, noise, t, loss_type, snr_gamma, vlb_weight, return_parts):
+        """p_losses after the model call."""
+        if self.variance_type != "learned_range":
+            if vlb_weight is not None or return_parts:
+                raise ValueError("vlb_weight and return_parts need variance_type='learned_range'")
+            if self._default_objective(snr_gamma):
+                return diffusion_loss(out, noise, loss_type)
+            return self._objective_loss(out, x_start, noise, t, loss_type, snr_gamma)
+        if loss_type not in ("l1", "l2", "huber"):
+            raise ValueError(f"Unknown loss type: {loss_type}")
+        vw = self._vlb_weight(vlb_weight)
+        _require_cuda(out, x_start, noise)
+        self._check_out(out, x_start)
+        dev = out.device
+        w = None if snr_gamma is None else self._snr_weights(snr_gamma, dev)
+        total, simple, vlb = _HybridFn.apply(
+            out, x_start.contiguous().float(), noise.contiguous().float(), t.to(dev).long().contiguous(),
+            self._tab("sqrt_alphas_cumprod", dev), self._tab("sqrt_one_minus_alphas_cumprod", dev), w,
+            self._lvar_table(dev), self.prediction_type, loss_type, vw)
+        return (total, simple, vlb) if return_parts else total
 
     def _snr_weights(self, gamma, dev):
         """[T] fp32 device table of min-SNR-gamma weights for the current prediction type, built and uploaded once
@@ -136,20 +224,28 @@ class ObjectiveMixin:
     def _cfg_pair(self, model, img, t, y):
         """DDPM._cfg_eps for either prediction type: a v output is converted to eps (both halves, one launch)
         before the guidance, which is affine with coefficients summing to 1 and so commutes with the conversion."""
+        return self._cfg_pair_out(model, img, t, y)[:2]
+
+    def _cfg_pair_out(self, model, img, t, y):
+        """(eps_cond, eps_uncond, the batched model output). With learned_range the two prediction halves are copied
+        contiguous first (one launch); the output's first B rows carry the conditional v, read in place by the step."""
         B = img.shape[0]
-        if self.prediction_type == "eps":
-            return DDPM._cfg_eps(model, img, t, y)
+        if self.prediction_type == "eps" and self.variance_type == "fixed":
+            return DDPM._cfg_eps(model, img, t, y) + (None,)
         both = model(torch.cat([img, img], 0), torch.cat([t, t], 0), torch.cat([y, torch.zeros_like(y)], 0))
-        eps, _ = self._convert(both, img, t, want_x0=False)
-        return eps[:B], eps[B:]
+        eps = self._pred_of(both, img)
+        if self.prediction_type == "v":
+            eps, _ = self._convert(eps, img, t, want_x0=False)
+        return eps[:B], eps[B:], both
 
 
 class DDPM(ObjectiveMixin, EditMixin, LikelihoodMixin):
     """DDPM diffusion process (diffusion/ddpm.py:15-332)."""
 
     def __init__(self, num_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule='linear', device='cuda',
-                 prediction_type='eps'):
+                 prediction_type='eps', variance_type='fixed'):
         self.prediction_type = _objective.check_prediction_type(prediction_type)
+        self.variance_type = _vlb.check_variance_type(variance_type)
         self.num_timesteps = num_timesteps
         self.device = device
         tabs = _schedule.build_tables(num_timesteps, beta_start, beta_end, beta_schedule)
@@ -175,16 +271,17 @@ class DDPM(ObjectiveMixin, EditMixin, LikelihoodMixin):
         return K.q_sample(x_start.float(), noise.float(), t.to(dev).long().contiguous(),
                           self._tab("sqrt_alphas_cumprod", dev), self._tab("sqrt_one_minus_alphas_cumprod", dev))
 
-    def p_losses(self, model, x_start, t, y=None, noise=None, loss_type='l2', snr_gamma=None):
+    def p_losses(self, model, x_start, t, y=None, noise=None, loss_type='l2', snr_gamma=None, vlb_weight=None,
+                 return_parts=False):
         """Training loss (diffusion/ddpm.py:106-140). Not in the reference: snr_gamma (min-SNR-gamma weighting) and
-        the v target of prediction_type='v', both through dmc_objective."""
+        the v target of prediction_type='v', both through dmc_objective; with variance_type='learned_range' the
+        hybrid loss L_simple + vlb_weight * L_vlb (arXiv:2102.09672 eq. 16; vlb_weight None: 0.001) through
+        dmc_hybrid_objective, and return_parts=True gives (total, simple, vlb_weight * L_vlb)."""
         if noise is None:
             noise = torch.randn_like(x_start)
         x_noisy = self.q_sample(x_start, t, noise)
         predicted_noise = model(x_noisy, t, y)
-        if self._default_objective(snr_gamma):
-            return diffusion_loss(predicted_noise, noise, loss_type)
-        return self._objective_loss(predicted_noise, x_start, noise, t, loss_type, snr_gamma)
+        return self._losses(predicted_noise, x_start, noise, t, loss_type, snr_gamma, vlb_weight, return_parts)
 
     def _extract(self, a, t, x_shape):
         batch_size = t.shape[0]
@@ -201,8 +298,41 @@ class DDPM(ObjectiveMixin, EditMixin, LikelihoodMixin):
                            x0=None if x0_pred is None else x0_pred.contiguous().float(),
                            z=None if z is None else z.contiguous().float())
 
-    def p_mean_variance(self, model, x, t, y=None, clip_denoised=True, eps=None, x0_pred=None):
-        """Posterior mean / variance / log-variance (diffusion/ddpm.py:151-195)."""
+    def _learned_inputs(self, model, x, t, y, eps, x0_pred, model_out):
+        """(model output, eps or None, x0 or None) of a learned_range step: the output's halves are read in place by
+        dmc_ddpm_step_learned unless an eps is given (guidance) or the prediction is v (converted from one contiguous
+        copy of the prediction half)."""
+        if eps is None:
+            model_out = model(x, t, y)
+            if self.prediction_type == "v":
+                eps, x0_pred = self._convert(self._pred_of(model_out, x), x, t)
+        elif model_out is None:
+            raise ValueError("variance_type='learned_range': an eps given to the step needs model_out, the model "
+                             "output whose second half is v")
+        _require_cuda(x, model_out)
+        return self._check_out(model_out, x).contiguous().float(), eps, x0_pred
+
+    def _step_learned(self, x, out, t, clip, eps, x0_pred, z):
+        dev = x.device
+        return K.ddpm_step_learned(x.contiguous().float(), out, t.to(dev).long().contiguous(),
+                                   self._tab("sqrt_recip_alphas_cumprod", dev),
+                                   self._tab("sqrt_recipm1_alphas_cumprod", dev),
+                                   self._tab("posterior_mean_coef1", dev), self._tab("posterior_mean_coef2", dev),
+                                   self._lvar_table(dev), clip=clip,
+                                   eps=None if eps is None else eps.contiguous().float(),
+                                   x0=None if x0_pred is None else x0_pred.contiguous().float(),
+                                   z=None if z is None else z.contiguous().float())
+
+    def p_mean_variance(self, model, x, t, y=None, clip_denoised=True, eps=None, x0_pred=None, model_out=None):
+        """Posterior mean / variance / log-variance (diffusion/ddpm.py:151-195). With learned_range the variance is the
+        model's: exp(lv_min + (v + 1)/2 * R) per element, of the model output's second half."""
+        if self.variance_type == "learned_range":
+            out, eps, x0_pred = self._learned_inputs(model, x, t, y, eps, x0_pred, model_out)
+            mean = self._step_learned(x, out, t, clip_denoised, eps, x0_pred, None)
+            tab = self._lvar_table(x.device)
+            logvar = (self._extract(tab[:, _vlb.L_LVMIN], t, x.shape)
+                      + (out[:, x.shape[1]:] + 1.0) * 0.5 * self._extract(tab[:, _vlb.L_R], t, x.shape))
+            return mean, logvar.exp(), logvar
         if eps is None:
             eps = model(x, t, y)
             if self.prediction_type == "v":
@@ -214,8 +344,16 @@ class DDPM(ObjectiveMixin, EditMixin, LikelihoodMixin):
         return mean, var, logvar
 
     @torch.no_grad()
-    def p_sample(self, model, x, t, y=None, clip_denoised=True, eps=None, x0_pred=None, noise=None):
-        """x_{t-1} ~ p(x_{t-1} | x_t) (diffusion/ddpm.py:197-220), one fused kernel after the model call."""
+    def p_sample(self, model, x, t, y=None, clip_denoised=True, eps=None, x0_pred=None, noise=None, model_out=None):
+        """x_{t-1} ~ p(x_{t-1} | x_t) (diffusion/ddpm.py:197-220), one fused kernel after the model call. With
+        learned_range the noise is scaled by the model's own standard deviation (dmc_ddpm_step_learned); a given eps
+        then comes with model_out, the model output that carries v."""
+        if self.variance_type == "learned_range":
+            out, eps, x0_pred = self._learned_inputs(model, x, t, y, eps, x0_pred, model_out)
+            if noise is None:
+                noise = torch.randn_like(x)
+            _require_cuda(x, noise)
+            return self._step_learned(x, out, t, clip_denoised, eps, x0_pred, noise)
         if eps is None:
             eps = model(x, t, y)
             if self.prediction_type == "v":
@@ -238,11 +376,13 @@ class DDPM(ObjectiveMixin, EditMixin, LikelihoodMixin):
     def _step_cfg(self, model, x, t, y, z, cfg_scale, p_threshold):
         """One step of sample_with_cfg(): shared with img2img / inpaint."""
         dev = x.device
-        eps_c, eps_u = self._cfg_pair(model, x, t, y)
+        eps_c, eps_u, both = self._cfg_pair_out(model, x, t, y)
         eps_g, x0 = K.cfg_x0(x.contiguous(), eps_c.contiguous(), eps_u.contiguous(), cfg_scale, t,
                              self._tab("sqrt_recip_alphas_cumprod", dev),
                              self._tab("sqrt_recipm1_alphas_cumprod", dev), 1, p_threshold)
-        return self.p_sample(model, x, t, y=None, clip_denoised=False, eps=eps_g, x0_pred=x0, noise=z)
+        # learned_range: the variance is the conditional half's (DiT's convention), the output's first B rows
+        cond = both[:x.shape[0]] if self.variance_type == "learned_range" else None
+        return self.p_sample(model, x, t, y=None, clip_denoised=False, eps=eps_g, x0_pred=x0, noise=z, model_out=cond)
 
     def _edit_steps(self):
         return self.num_timesteps
@@ -259,7 +399,7 @@ class DDPM(ObjectiveMixin, EditMixin, LikelihoodMixin):
                 return self._step_plain(model, x, args[0], yy, z)
             return self._step_cfg(model, x, args[0], yy, z, cfg_scale, p_threshold)
 
-        key = ("ddpm", self.prediction_type, T, y is not None, cfg_scale, p_threshold, self.alphas_cumprod.data_ptr())
+        key = ("ddpm", self.prediction_type, self.variance_type, T, y is not None, cfg_scale, p_threshold, self.alphas_cumprod.data_ptr())
         return ts, (lambda j: (tab[j],)), step, True, key
 
     @torch.no_grad()

@@ -28,7 +28,7 @@ class DPMSolver(DDIM):
 
     def __init__(self, num_timesteps=1000, num_inference_steps=20, beta_start=0.0001, beta_end=0.02,
                  beta_schedule='linear', solver_order=2, timestep_spacing='logsnr', lower_order_final=True,
-                 device='cuda', prediction_type='eps'):
+                 device='cuda', prediction_type='eps', variance_type='fixed'):
         if solver_order not in (1, 2):
             raise ValueError(f"solver_order must be 1 or 2, got {solver_order}")
         if timestep_spacing not in _dpm.SPACINGS:
@@ -37,7 +37,7 @@ class DPMSolver(DDIM):
         self.timestep_spacing = timestep_spacing
         self.lower_order_final = bool(lower_order_final)
         super().__init__(num_timesteps, num_inference_steps, beta_start, beta_end, beta_schedule, eta=0.0,
-                         device=device, prediction_type=prediction_type)
+                         device=device, prediction_type=prediction_type, variance_type=variance_type)
 
     def _setup_inference_timesteps(self):
         """num_inference_steps keeps the request; with 'logsnr' len(inference_timesteps) can be below it."""
@@ -68,7 +68,7 @@ class DPMSolver(DDIM):
         return st
 
     def _key(self, tag, coef, *rest):
-        return (tag, self.prediction_type, self.solver_order, self.timestep_spacing, self.lower_order_final,
+        return (tag, self.prediction_type, self.variance_type, self.solver_order, self.timestep_spacing, self.lower_order_final,
                 coef.shape[0], coef.data_ptr()) + rest
 
     def _run(self, model, st, S, inputs, fn, return_all_timesteps, key, const, desc):
@@ -91,7 +91,7 @@ class DPMSolver(DDIM):
     def _step_plain(self, model, st, t, k, y, coef, shared_t, clip=True):
         """One step of sample(): shared with img2img / inpaint."""
         x = st[0]
-        eps = model(x, t[:1] if shared_t else t, y)
+        eps = self._pred_of(model(x, t[:1] if shared_t else t, y), x)    # learned_range: v is ignored, one copy
         new = torch.empty_like(st)
         if self.prediction_type == "v":
             _, x0 = self._convert(eps, x, t)

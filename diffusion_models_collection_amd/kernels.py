@@ -763,6 +763,127 @@ def vlb_step(x0, x_t, pred, t, coef, clip=True, z_next=None, t_next=None, sa=Non
     return tuple(rows)
 
 
+def _lvar_coef(what, coef, dev):
+    if (coef is None or coef.dim() != 2 or coef.shape[1] != L.LVAR_COLS or coef.shape[0] < 1
+            or coef.dtype != torch.float32 or coef.device != dev or not coef.is_contiguous()):
+        raise L.DMCError(f"{what}: coef must be a contiguous fp32 [T, {L.LVAR_COLS}] tensor on {dev} "
+                         "(diffusion/_vlb.py learned_coefficients)")
+    return coef.shape[0]
+
+
+def _halves(what, out, ref):
+    """(prediction half, v half, row stride) of a model output [N, 2C, ...] for ref = [N, C, ...]: views, read in place."""
+    if (out.dim() != ref.dim() or out.shape[0] != ref.shape[0] or out.shape[1] != 2 * ref.shape[1]
+            or out.shape[2:] != ref.shape[2:] or out.device != ref.device):
+        raise L.DMCError(f"{what}: the model output is {tuple(out.shape)} on {out.device}, expected twice the channels of "
+                         f"{tuple(ref.shape)} on {ref.device}")
+    _fp32_contig(what, out)
+    C = ref.shape[1]
+    return out[:, :C], out[:, C:], out.stride(0)
+
+
+def hybrid_objective(pred_type, loss_type, out, x0, noise, t, sa, s1, coef, w=None, vlb_weight=0.001, dloss=None,
+                     grad=True, dout=None):
+    """L_simple + vlb_weight * mean_n vb_n and its gradient in one pass (dmc_hybrid_objective). out: the model output
+    [N, 2C, ...], prediction half then v; x0, noise: [N, C, ...]; coef: the [T, 8] table of
+    diffusion/_vlb.py learned_coefficients. Returns (loss[3] = {total, simple, vlb}, dout or None)."""
+    what = "dmc_hybrid_objective"
+    code = _pred_code(what, pred_type)
+    if loss_type not in L.LOSS:
+        raise L.DMCError(f"{what}: unknown loss type {loss_type!r}")
+    if not x0.is_cuda or x0.dim() < 2 or x0.numel() < 1:
+        raise L.DMCError(f"{what}: x0 must be a non-empty [N, C, ...] device tensor, got {tuple(x0.shape)} on "
+                         f"{x0.device}")
+    N, dev = x0.shape[0], x0.device
+    _halves(what, out, x0)
+    _same(x0, noise, what=what)
+    _fp32_contig(what, x0, noise)
+    if t is None:
+        raise L.DMCError(f"{what}: needs timesteps")
+    _steps(N, dev, t, what=what)
+    T = _lvar_coef(what, coef, dev)
+    if _tables(what, dev, sa, s1, w) not in (None, T) or (code == L.PRED["v"] and (sa is None or s1 is None)):
+        raise L.DMCError(f"{what}: sa, s1 and w must be [T = {T}] tables (sa and s1 are needed for v-prediction)")
+    if grad:
+        if dloss is None or dloss.numel() != 1 or dloss.dtype != torch.float32 or dloss.device != dev:
+            raise L.DMCError(f"{what}: dloss must be one fp32 value on {dev}")
+        dout = torch.empty_like(out) if dout is None else dout
+        _same(out, dout, what=what)
+        _fp32_contig(what, dout)
+    else:
+        dout = None
+    loss = torch.empty(3, dtype=torch.float32, device=dev)
+    ws = SCRATCH.get(2 * L.OBJECTIVE_MAX_BLOCKS * N * 4, dev)
+    check(LIB.dmc_hybrid_objective(code, L.LOSS[loss_type], ptr(out), ptr(x0), ptr(noise), ptr(t), ptr(sa), ptr(s1),
+                                   ptr(w), ptr(coef), T, N, x0.numel() // N, float(vlb_weight),
+                                   ptr(dloss) if grad else None, ptr(loss), ptr(dout), ptr(ws), L.stream()), what)
+    return loss, dout
+
+
+def vlb_step_learned(x0, x_t, out, t, coef, clip=True, z_next=None, t_next=None, sa=None, s1=None, x_next=None,
+                     rows=None):
+    """dmc_vlb_step with the learned variance (dmc_vlb_step_learned): out is the model output [N, 2C, ...], both halves
+    read in place; coef the [T, 8] table of diffusion/_vlb.py learned_coefficients. Otherwise as vlb_step (rows: the
+    four [N] buffers to fill)."""
+    what = "dmc_vlb_step_learned"
+    if not x0.is_cuda or x0.dim() < 2 or x0.numel() < 1:
+        raise L.DMCError(f"{what}: x0 must be a non-empty [N, C, ...] device tensor, got {tuple(x0.shape)} on "
+                         f"{x0.device}")
+    N, dev = x0.shape[0], x0.device
+    pred, v, ld = _halves(what, out, x0)
+    _same(x0, x_t, z_next, x_next, what=what)
+    _fp32_contig(what, x0, x_t, z_next, x_next)
+    if t is None:
+        raise L.DMCError(f"{what}: needs timesteps")
+    _steps(N, dev, t, t_next, what=what)
+    T = _lvar_coef(what, coef, dev)
+    if x_next is not None:
+        if z_next is None or t_next is None or _tables(what, dev, sa, s1) != T or sa is None or s1 is None:
+            raise L.DMCError(f"{what}: x_next needs z_next, t_next and the [T = {T}] sqrt_alphas_cumprod / "
+                             "sqrt_one_minus_alphas_cumprod tables")
+    rows = rows if rows is not None else tuple(torch.empty(N, dtype=torch.float32, device=dev) for _ in range(4))
+    if len(rows) != 4:
+        raise L.DMCError(f"{what}: rows must hold the four [N] buffers vb, xstart_mse, eps_mse, x0_sq")
+    for r in rows:
+        if r.shape != (N,) or r.device != dev:
+            raise L.DMCError(f"{what}: an output row is {tuple(r.shape)} on {r.device}, expected ({N},) on {dev}")
+    _fp32_contig(what, *rows)
+    ws = SCRATCH.get(4 * L.VLB_MAX_BLOCKS * N * 4, dev)
+    nxt = x_next is not None
+    check(LIB.dmc_vlb_step_learned(ptr(x0), ptr(x_t), ptr(pred), ld, ptr(v), ld, ptr(t), ptr(coef), T, int(bool(clip)),
+                                   ptr(z_next) if nxt else None, ptr(t_next) if nxt else None,
+                                   ptr(sa) if nxt else None, ptr(s1) if nxt else None, N, x0.numel() // N, ptr(x_next),
+                                   ptr(rows[0]), ptr(rows[1]), ptr(rows[2]), ptr(rows[3]), ptr(ws), L.stream()), what)
+    return tuple(rows)
+
+
+def ddpm_step_learned(x, out, t, sra, srm1, c1, c2, coef, clip=True, eps=None, x0=None, z=None, res=None):
+    """DDPM step with the learned variance (dmc_ddpm_step_learned). out: the model output [N, 2C, ...]; its v half is
+    read in place, and so is its prediction half unless eps (a contiguous [N, C, ...] eps: the guided or converted one)
+    is given; x0 (optional, with eps) replaces the x0 prediction. z None: the mean, with dmc_ddpm_step's bits."""
+    what = "dmc_ddpm_step_learned"
+    if not x.is_cuda or x.dim() < 2 or x.numel() < 1:
+        raise L.DMCError(f"{what}: x must be a non-empty [N, C, ...] device tensor, got {tuple(x.shape)} on {x.device}")
+    N, dev = x.shape[0], x.device
+    per = x.numel() // N
+    pred, v, ld = _halves(what, out, x)
+    if x0 is not None and eps is None:
+        raise L.DMCError(f"{what}: x0 comes with the eps it was formed from")
+    res = torch.empty_like(x) if res is None else res
+    _same(x, eps, x0, z, res, what=what)
+    _fp32_contig(what, x, eps, x0, z, res)
+    if t is None:
+        raise L.DMCError(f"{what}: needs timesteps")
+    _steps(N, dev, t, what=what)
+    T = _lvar_coef(what, coef, dev)
+    if _tables(what, dev, sra, srm1, c1, c2) != T or any(tab is None for tab in (sra, srm1, c1, c2)):
+        raise L.DMCError(f"{what}: needs the four [T = {T}] sqrt_recip / posterior_mean_coef tables")
+    e, eld = (pred, ld) if eps is None else (eps, per)
+    check(LIB.dmc_ddpm_step_learned(ptr(x), ptr(e), eld, ptr(v), ld, ptr(x0), ptr(t), ptr(sra), ptr(srm1), ptr(c1),
+                                    ptr(c2), ptr(coef), T, N, per, int(bool(clip)), ptr(z), ptr(res), L.stream()), what)
+    return res
+
+
 def ddim_step(x, eps, t, t_next, alphas_cumprod, eta=0.0, clip=True, x0=None, z=None, out=None):
     if out is None:
         out = torch.empty_like(x)

@@ -146,6 +146,7 @@ class DiM(nn.Module):
         dropout=0.1,
         compute_dtype=None,
         mixer=None,
+        learn_sigma=False,
     ):
         mixer = _resolve_mixer(mixer)
         dt = _resolve_dtype(compute_dtype)
@@ -167,7 +168,10 @@ class DiM(nn.Module):
         self.img_size = tuple(img_size)
         self.patch_size = patch_size
         self.in_channels = in_channels
-        self.out_channels = in_channels
+        # not in the reference: a variance head (the original DiT's learn_sigma) doubles the final projection; the
+        # output is [B, 2C, H, W], the prediction then v (diffusion variance_type='learned_range')
+        self.learn_sigma = bool(learn_sigma)
+        self.out_channels = 2 * in_channels if self.learn_sigma else in_channels
         self.hidden_size = hidden_size
         self.state_size = state_size
         self.num_classes = num_classes

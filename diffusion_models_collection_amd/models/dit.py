@@ -115,6 +115,7 @@ class DiT(nn.Module):
         num_classes=None,
         dropout=0.1,
         compute_dtype=None,
+        learn_sigma=False,
     ):
         super().__init__()
         if isinstance(img_size, int):
@@ -124,7 +125,10 @@ class DiT(nn.Module):
         self.img_size = (img_h, img_w)
         self.patch_size = patch_size
         self.in_channels = in_channels
-        self.out_channels = in_channels
+        # not in the reference: a variance head (the original DiT's learn_sigma) doubles the final projection; the
+        # output is [B, 2C, H, W], the prediction then v (diffusion variance_type='learned_range')
+        self.learn_sigma = bool(learn_sigma)
+        self.out_channels = 2 * in_channels if self.learn_sigma else in_channels
         self.hidden_size = hidden_size
         self.num_heads = num_heads
         self.num_classes = num_classes

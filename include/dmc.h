@@ -434,6 +434,48 @@ int dmc_vlb_step(const float* x0, const float* x_t, const float* pred, const int
                  int N, int per_sample, float* x_next, float* vb, float* xstart_mse, float* eps_mse,
                  float* x0_sq, float* workspace, void* stream);
 
+/* Learned variances (Nichol & Dhariwal 2021, arXiv:2102.09672 §3.1); not in the reference. The model returns
+ * [N][2][per_sample]: the prediction (eps or v), then v, the interpolation of the log-variance between the posterior's
+ * and beta's. coef: [T][DMC_LVAR_COLS] fp32 rows {c_x, c_p, c1, lv_min, R, kmin, keps, lv_max}
+ * (diffusion/_vlb.py learned_coefficients); t[n], clamped into [0, T), picks sample n's row. Per element
+ *   d = (v + 1)/2 * R  (not clamped);   lv_p = lv_min + d;   delta = x0 - x0_pred
+ *   t > 0:   term = 0.5*(d + expm1(-d)) + kmin*exp(-d)*delta^2       -- KL against the true posterior, nats
+ *            d term / d v = (-0.5*expm1(-d) - kmin*exp(-d)*delta^2) * 0.5*R
+ *   t == 0:  term = dmc_vlb_step's decoder -log p with isig = exp(-0.5*lv_p) per element
+ *            d term / d v = 0.5*(zp*phi(zp) - zm*phi(zm)) / p * 0.5*R, an absent edge's z dropped; 0 on the 1e-12 floor
+ * One device function computes the term for all three entries. 16-byte accesses when per_sample % 4 == 0, every row
+ * stride is a multiple of 4 and every pointer read or written (the v half's base included) is 16-byte aligned,
+ * element-wise otherwise.
+ *
+ * dmc_hybrid_objective: L_hybrid = L_simple + vlb_weight * mean_n vb_n and its gradient in ONE pass. out, dout:
+ * [N][2][per_sample]; x0, noise: [N][per_sample]. L_simple is dmc_objective on the prediction half (pred_type,
+ * loss_type, w as there; with vlb_weight == 0 loss[1] and dout's prediction half have dmc_objective's bits). vb_n is the
+ * per-sample mean of the term / ln 2 with delta = c_p*(pred - target), so x_t is not needed. The term sends no gradient
+ * to the prediction half (the paper's stop-gradient): dout's v half = dloss[0] * vlb_weight / (N*per_sample*ln 2) *
+ * d term / d v. loss[3] = {simple + vlb, simple, vlb_weight * mean_n vb_n}. dout == NULL: forward only.
+ * workspace: >= DMC_HYBRID_WORKSPACE_FLOATS(N) floats; block partials per sample added in block order, samples in
+ * index order: no atomics, deterministic. sa, s1 are read for DMC_PRED_V only. */
+#define DMC_LVAR_COLS 8
+#define DMC_HYBRID_WORKSPACE_FLOATS(N) (2 * DMC_OBJECTIVE_MAX_BLOCKS * (size_t)(N))
+int dmc_hybrid_objective(int pred_type, int loss_type, const float* out, const float* x0, const float* noise,
+                         const int64_t* t, const float* sa, const float* s1, const float* w, const float* coef,
+                         int T, int N, int per_sample, float vlb_weight, const float* dloss, float* loss,
+                         float* dout, float* workspace, void* stream);
+/* dmc_vlb_step with the learned term: pred and v are given as a base pointer and a row stride in floats (the two halves
+ * of the model output, read in place). Outputs, the x_next contract, clip and the workspace as dmc_vlb_step. */
+int dmc_vlb_step_learned(const float* x0, const float* x_t, const float* pred, long pred_stride, const float* v,
+                         long v_stride, const int64_t* t, const float* coef, int T, int clip, const float* z_next,
+                         const int64_t* t_next, const float* sa, const float* s1, int N, int per_sample,
+                         float* x_next, float* vb, float* xstart_mse, float* eps_mse, float* x0_sq,
+                         float* workspace, void* stream);
+/* dmc_ddpm_step with the learned variance: out = mean + [t != 0] exp(0.5*(lv_min + d)) * z, the mean by dmc_ddpm_step's
+ * ops from the same four [T] tables (z == NULL: its bits; v is then unread). eps and v: base pointer and row stride in
+ * floats. eps may be NULL with x0_in. t is clamped into [0, T). */
+int dmc_ddpm_step_learned(const float* x, const float* eps, long eps_stride, const float* v, long v_stride,
+                          const float* x0_in, const int64_t* t, const float* sqrt_recip_ac,
+                          const float* sqrt_recipm1_ac, const float* coef1, const float* coef2, const float* coef,
+                          int T, int N, int per_sample, int clip, const float* z, float* out, void* stream);
+
 /* DDIM.p_sample update (diffusion/ddim.py:154-208), fused; alpha gathers on device; if any
  * t_next < 0 the reference uses alpha_next = 1 for the whole batch (:176-179), so does this.
  * x0_in (optional) replaces the x0 prediction; z (optional) is the eta>0 noise. */
