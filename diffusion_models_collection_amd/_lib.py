@@ -175,12 +175,18 @@ def _load():
         "dmc_loss_bwd": (_c_int, [_c_int, _c_p, _c_p, _c_long, _c_p, _c_p, _c_p]),
         "dmc_objective": (_c_int, [_c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int,
                                    _c_p, _c_p, _c_p, _c_p, _c_p]),
+        "dmc_objective_is": (_c_int, [_c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int,
+                                      _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
         "dmc_pred_convert": (_c_int, [_c_int, _c_p, _c_p, _c_p, _c_p, _c_int, _c_p, _c_int, _c_int, _c_int, _c_p,
                                       _c_p, _c_p]),
         "dmc_vlb_step": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int,
                                   _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
         "dmc_hybrid_objective": (_c_int, [_c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int,
                                           _c_int, _c_int, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p]),
+        "dmc_hybrid_objective_is": (_c_int, [_c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int,
+                                             _c_int, _c_int, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
+        "dmc_ts_history_update": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p]),
+        "dmc_ts_sample": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_f, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p]),
         "dmc_vlb_step_learned": (_c_int, [_c_p, _c_p, _c_p, _c_long, _c_p, _c_long, _c_p, _c_p, _c_int, _c_int, _c_p,
                                           _c_p, _c_p, _c_p, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
                                           _c_p]),

@@ -23,9 +23,11 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("DMC_OFFLOAD_ARCH", "gfx950")
 
 SOURCES = ["dmc_conv.hip", "dmc_wgrad.hip", "dmc_norm.hip", "dmc_attn.hip", "dmc_elem.hip", "dmc_dit.hip", "dmc_mamba.hip",
-           "dmc_data.hip"]
-# the element-wise and data files restate torch op sequences: no FMA contraction there
-EXTRA = {"dmc_elem.hip": ["-ffp-contract=off"], "dmc_data.hip": ["-ffp-contract=off"]}
+           "dmc_data.hip", "dmc_resample.hip"]
+# the element-wise and data files restate torch op sequences, the resampling file a numpy float64 one: no FMA
+# contraction there
+EXTRA = {"dmc_elem.hip": ["-ffp-contract=off"], "dmc_data.hip": ["-ffp-contract=off"],
+         "dmc_resample.hip": ["-ffp-contract=off"]}
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
           "-Wno-unused-variable", "-I", str(INCLUDE), "-I", str(CSRC)]
 

@@ -240,11 +240,15 @@ DMC_DEV long clamp_t(long t, int T) { return t < 0 ? 0 : (t > T - 1 ? T - 1 : t)
 // Grid as dpm_step_kernel: blockIdx.y strides over samples, blockIdx.x over the sample's elements, so t and the
 // table entries are block-uniform, read once per sample. Block (bx, n) leaves its sum at partial[n * gridDim.x + bx];
 // pred / x0 / noise are read once and dpred written once in that same pass. x0 is read for v-prediction only.
-template <bool VEC>
+// IS (dmc_objective_is with a table): iw[t_n] is the sample's importance weight, the gradient's LAST factor, so dpred is
+// iw[t_n] times dmc_objective's dpred rounded once, and with 1 its bits. Without IS iw is unread and the code is
+// dmc_objective's as it was.
+template <bool VEC, bool IS>
 __global__ __launch_bounds__(256) void objective_kernel(int pred_type, int type, const float* pred, const float* x0,
                                                         const float* noise, const int64_t* t, const float* sa,
-                                                        const float* s1, const float* w, int T, int N, int per,
-                                                        const float* dloss, float* dpred, float* partial) {
+                                                        const float* s1, const float* w, const float* iw, int T,
+                                                        int N, int per, const float* dloss, float* dpred,
+                                                        float* partial) {
   __shared__ float red[4];
   const bool grad = dpred != nullptr;
   const bool isv = pred_type == DMC_PRED_V;
@@ -254,6 +258,7 @@ __global__ __launch_bounds__(256) void objective_kernel(int pred_type, int type,
     const float san = isv ? sa[tt] : 0.f, s1n = isv ? s1[tt] : 0.f;
     float scale = g;
     if (w) scale = g * w[tt];
+    const float iwn = IS ? iw[tt] : 1.f;
     const size_t base = (size_t)n * per;
     float s = 0.f;
     if (VEC) {
@@ -268,7 +273,7 @@ __global__ __launch_bounds__(256) void objective_kernel(int pred_type, int type,
         for (int k = 0; k < 4; ++k) {
           float dp = 0.f;
           s += obj_elem(pred_type, type, san, s1n, pv[k], xv[k], ev[k], grad, scale, dp);
-          dv[k] = dp;
+          dv[k] = IS ? dp * iwn : dp;
         }
         if (grad) *(v4f*)(dpred + i) = dv;
       }
@@ -277,7 +282,7 @@ __global__ __launch_bounds__(256) void objective_kernel(int pred_type, int type,
         const size_t i = base + q;
         float dp = 0.f;
         s += obj_elem(pred_type, type, san, s1n, pred[i], isv ? x0[i] : 0.f, noise[i], grad, scale, dp);
-        if (grad) dpred[i] = dp;
+        if (grad) dpred[i] = IS ? dp * iwn : dp;
       }
     }
     s = wave_sum(s);
@@ -289,9 +294,11 @@ __global__ __launch_bounds__(256) void objective_kernel(int pred_type, int type,
 }
 
 // loss = (1/N) sum_n w[t_n] * (1/per) * (sample n's partials in block order), samples added in index order by one
-// thread: a fixed order, no atomics.
+// thread: a fixed order, no atomics. dmc_objective_is: row_loss[n] (if given) is sample n's term of that sum, and the
+// term enters the sum times iw[t_n] (NULL: as it is).
 __global__ __launch_bounds__(256) void objective_final_kernel(const float* partial, int gx, const int64_t* t,
-                                                              const float* w, int T, int N, int per, float* loss) {
+                                                              const float* w, const float* iw, int T, int N, int per,
+                                                              float* loss, float* row_loss) {
   __shared__ float sm[256];
   float total = 0.f;
   for (int n0 = 0; n0 < N; n0 += 256) {
@@ -302,6 +309,8 @@ __global__ __launch_bounds__(256) void objective_final_kernel(const float* parti
       for (int b = 0; b < gx; ++b) s += partial[(size_t)n * gx + b];
       m = s / (float)per;
       if (w) m = w[clamp_t(t[n], T)] * m;
+      if (row_loss) row_loss[n] = m;
+      if (iw) m = iw[clamp_t(t[n], T)] * m;
     }
     sm[threadIdx.x] = m;
     __syncthreads();
@@ -566,11 +575,12 @@ DMC_DEV float lvar_term(const LvarRow& r, bool dec, float x0, float delta, float
 // gradient keep dmc_objective's bits), the v half gets the term with delta = c_p*(pred - target), which needs neither
 // x_t nor a division. The term sends no gradient to the prediction half. Block (bx, n) leaves {simple, term} sums at
 // partial[(n * gridDim.x + bx) * 2 ..]. x0 is read where the sample needs it: v-prediction, or t = 0 (the edges).
-template <bool VEC, bool GRAD>
+// IS and iw as in objective_kernel: the last factor of both halves' gradient.
+template <bool VEC, bool GRAD, bool IS>
 __global__ __launch_bounds__(256) void hybrid_objective_kernel(int pred_type, int type, const float* out,
                                                                const float* x0, const float* noise, const int64_t* t,
                                                                const float* sa, const float* s1, const float* w,
-                                                               const float* coef, int T, int N, int per,
+                                                               const float* iw, const float* coef, int T, int N, int per,
                                                                float vlb_weight, const float* dloss, float* dout,
                                                                float* partial) {
   __shared__ float red[2][4];
@@ -585,6 +595,7 @@ __global__ __launch_bounds__(256) void hybrid_objective_kernel(int pred_type, in
     const bool dec = tt == 0, rdx = isv || dec;
     float scale = g;
     if (w) scale = g * w[tt];
+    const float iwn = IS ? iw[tt] : 1.f;
     const size_t xbase = (size_t)n * per, obase = 2 * xbase;
     float ss = 0.f, sv = 0.f;
     if (VEC) {
@@ -602,8 +613,8 @@ __global__ __launch_bounds__(256) void hybrid_objective_kernel(int pred_type, in
           ss += obj_elem(pred_type, type, san, s1n, pv[k], xv[k], ev[k], GRAD, scale, dp);
           const float delta = cp * (pv[k] - obj_target(pred_type, san, s1n, xv[k], ev[k]));
           sv += lvar_term<GRAD>(r, dec, xv[k], delta, vv[k], dv);
-          dpv[k] = dp;
-          dvv[k] = gv * dv;
+          dpv[k] = IS ? dp * iwn : dp;
+          dvv[k] = IS ? (gv * dv) * iwn : gv * dv;
         }
         if (GRAD) {
           *(v4f*)(dout + o) = dpv;
@@ -619,8 +630,8 @@ __global__ __launch_bounds__(256) void hybrid_objective_kernel(int pred_type, in
         const float delta = cp * (p - obj_target(pred_type, san, s1n, xx, e));
         sv += lvar_term<GRAD>(r, dec, xx, delta, out[o + per], dv);
         if (GRAD) {
-          dout[o] = dp;
-          dout[o + per] = gv * dv;
+          dout[o] = IS ? dp * iwn : dp;
+          dout[o + per] = IS ? (gv * dv) * iwn : gv * dv;
         }
       }
     }
@@ -641,9 +652,11 @@ __global__ __launch_bounds__(256) void hybrid_objective_kernel(int pred_type, in
 
 // objective_final_kernel's order for both sums: loss = {simple + vlb, simple, vlb}, simple as dmc_objective's loss[0],
 // vlb = vlb_weight * (1/N) sum_n (1/per) * (sample n's term partials in block order) / ln 2.
+// dmc_hybrid_objective_is: row_loss[n] = simple_n + vlb_weight * vb_n of the two per-sample terms, which enter their sums
+// times iw[t_n] (NULL: as they are).
 __global__ __launch_bounds__(256) void hybrid_final_kernel(const float* partial, int gx, const int64_t* t,
-                                                           const float* w, int T, int N, int per, float vlb_weight,
-                                                           float* loss) {
+                                                           const float* w, const float* iw, int T, int N, int per,
+                                                           float vlb_weight, float* loss, float* row_loss) {
   __shared__ float sm[2][256];
   float total = 0.f, totalv = 0.f;
   for (int n0 = 0; n0 < N; n0 += 256) {
@@ -658,6 +671,12 @@ __global__ __launch_bounds__(256) void hybrid_final_kernel(const float* partial,
       m = s / (float)per;
       if (w) m = w[clamp_t(t[n], T)] * m;
       mv = (sv / (float)per) / 0.69314718055994531f;
+      if (row_loss) row_loss[n] = m + vlb_weight * mv;
+      if (iw) {
+        const float iwn = iw[clamp_t(t[n], T)];
+        m = iwn * m;
+        mv = iwn * mv;
+      }
     }
     sm[0][threadIdx.x] = m;
     sm[1][threadIdx.x] = mv;
@@ -1374,9 +1393,11 @@ inline dim3 sample_grid(int units, int N, int xcap) {
 }
 }  // namespace
 
-extern "C" int dmc_objective(int pred_type, int type, const float* pred, const float* x0, const float* noise,
-                             const int64_t* t, const float* sa, const float* s1, const float* w, int T, int N, int per,
-                             const float* dloss, float* loss, float* dpred, float* ws, void* stream) {
+// dmc_objective and dmc_objective_is: the same two kernels, iw and row_loss NULL for the former
+static int objective_launch(const char* what, int pred_type, int type, const float* pred, const float* x0,
+                            const float* noise, const int64_t* t, const float* sa, const float* s1, const float* w,
+                            const float* iw, int T, int N, int per, const float* dloss, float* loss, float* row_loss,
+                            float* dpred, float* ws, void* stream) {
   DMC_REQUIRE(pred_type == DMC_PRED_EPS || pred_type == DMC_PRED_V, "objective: prediction type %d", pred_type);
   DMC_REQUIRE(type >= 0 && type <= 2, "objective: loss type %d", type);
   DMC_REQUIRE(T > 0 && N > 0 && per > 0, "objective: T %d, N %d, per_sample %d must be positive", T, N, per);
@@ -1388,14 +1409,31 @@ extern "C" int dmc_objective(int pred_type, int type, const float* pred, const f
   const bool vec = per % 4 == 0 && (bits & 15) == 0;
   const dim3 grid = sample_grid(vec ? per / 4 : per, N, DMC_OBJECTIVE_MAX_BLOCKS);
   hipStream_t s = dmc::as_stream(stream);
-  if (vec)
-    objective_kernel<true><<<grid, 256, 0, s>>>(pred_type, type, pred, x0, noise, t, sa, s1, w, T, N, per, dloss, dpred,
-                                                ws);
-  else
-    objective_kernel<false><<<grid, 256, 0, s>>>(pred_type, type, pred, x0, noise, t, sa, s1, w, T, N, per, dloss,
-                                                 dpred, ws);
-  objective_final_kernel<<<1, 256, 0, s>>>(ws, (int)grid.x, t, w, T, N, per, loss);
-  return dmc::check_launch("dmc_objective");
+#define DMC_OBJECTIVE_LAUNCH(VEC, IS)                                                                                 \
+  objective_kernel<VEC, IS><<<grid, 256, 0, s>>>(pred_type, type, pred, x0, noise, t, sa, s1, w, iw, T, N, per, dloss, \
+                                                 dpred, ws)
+  if (vec && iw) DMC_OBJECTIVE_LAUNCH(true, true);
+  else if (vec) DMC_OBJECTIVE_LAUNCH(true, false);
+  else if (iw) DMC_OBJECTIVE_LAUNCH(false, true);
+  else DMC_OBJECTIVE_LAUNCH(false, false);
+#undef DMC_OBJECTIVE_LAUNCH
+  objective_final_kernel<<<1, 256, 0, s>>>(ws, (int)grid.x, t, w, iw, T, N, per, loss, row_loss);
+  return dmc::check_launch(what);
+}
+
+extern "C" int dmc_objective(int pred_type, int type, const float* pred, const float* x0, const float* noise,
+                             const int64_t* t, const float* sa, const float* s1, const float* w, int T, int N, int per,
+                             const float* dloss, float* loss, float* dpred, float* ws, void* stream) {
+  return objective_launch("dmc_objective", pred_type, type, pred, x0, noise, t, sa, s1, w, nullptr, T, N, per, dloss,
+                          loss, nullptr, dpred, ws, stream);
+}
+
+extern "C" int dmc_objective_is(int pred_type, int type, const float* pred, const float* x0, const float* noise,
+                                const int64_t* t, const float* sa, const float* s1, const float* w, const float* iw,
+                                int T, int N, int per, const float* dloss, float* loss, float* row_loss, float* dpred,
+                                float* ws, void* stream) {
+  return objective_launch("dmc_objective_is", pred_type, type, pred, x0, noise, t, sa, s1, w, iw, T, N, per, dloss,
+                          loss, row_loss, dpred, ws, stream);
 }
 
 extern "C" int dmc_pred_convert(int pred_type, const float* x, const int64_t* t, const float* sa, const float* s1,
@@ -1437,10 +1475,11 @@ extern "C" int dmc_vlb_step(const float* x0, const float* x_t, const float* pred
   return dmc::check_launch("dmc_vlb_step");
 }
 
-extern "C" int dmc_hybrid_objective(int pred_type, int type, const float* out, const float* x0, const float* noise,
-                                    const int64_t* t, const float* sa, const float* s1, const float* w,
-                                    const float* coef, int T, int N, int per, float vlb_weight, const float* dloss,
-                                    float* loss, float* dout, float* ws, void* stream) {
+// dmc_hybrid_objective and dmc_hybrid_objective_is, as objective_launch
+static int hybrid_launch(const char* what, int pred_type, int type, const float* out, const float* x0,
+                         const float* noise, const int64_t* t, const float* sa, const float* s1, const float* w,
+                         const float* iw, const float* coef, int T, int N, int per, float vlb_weight,
+                         const float* dloss, float* loss, float* row_loss, float* dout, float* ws, void* stream) {
   DMC_REQUIRE(pred_type == DMC_PRED_EPS || pred_type == DMC_PRED_V, "hybrid_objective: prediction type %d", pred_type);
   DMC_REQUIRE(type >= 0 && type <= 2, "hybrid_objective: loss type %d", type);
   DMC_REQUIRE(T > 0 && N > 0 && per > 0, "hybrid_objective: T %d, N %d, per_sample %d must be positive", T, N, per);
@@ -1453,15 +1492,38 @@ extern "C" int dmc_hybrid_objective(int pred_type, int type, const float* out, c
   const dim3 grid = sample_grid(vec ? per / 4 : per, N, DMC_OBJECTIVE_MAX_BLOCKS);
   hipStream_t s = dmc::as_stream(stream);
 #define DMC_HYBRID_LAUNCH(VEC, GRAD)                                                                                  \
-  hybrid_objective_kernel<VEC, GRAD><<<grid, 256, 0, s>>>(pred_type, type, out, x0, noise, t, sa, s1, w, coef, T, N,  \
-                                                          per, vlb_weight, dloss, dout, ws)
+  do {                                                                                                                \
+    if (iw && GRAD)   /* the forward alone never reads iw */                                                          \
+      hybrid_objective_kernel<VEC, GRAD, true><<<grid, 256, 0, s>>>(pred_type, type, out, x0, noise, t, sa, s1, w, iw, \
+                                                                    coef, T, N, per, vlb_weight, dloss, dout, ws);    \
+    else                                                                                                              \
+      hybrid_objective_kernel<VEC, GRAD, false><<<grid, 256, 0, s>>>(pred_type, type, out, x0, noise, t, sa, s1, w,   \
+                                                                     iw, coef, T, N, per, vlb_weight, dloss, dout, ws); \
+  } while (0)
   if (vec && dout) DMC_HYBRID_LAUNCH(true, true);
   else if (vec) DMC_HYBRID_LAUNCH(true, false);
   else if (dout) DMC_HYBRID_LAUNCH(false, true);
   else DMC_HYBRID_LAUNCH(false, false);
 #undef DMC_HYBRID_LAUNCH
-  hybrid_final_kernel<<<1, 256, 0, s>>>(ws, (int)grid.x, t, w, T, N, per, vlb_weight, loss);
-  return dmc::check_launch("dmc_hybrid_objective");
+  hybrid_final_kernel<<<1, 256, 0, s>>>(ws, (int)grid.x, t, w, iw, T, N, per, vlb_weight, loss, row_loss);
+  return dmc::check_launch(what);
+}
+
+extern "C" int dmc_hybrid_objective(int pred_type, int type, const float* out, const float* x0, const float* noise,
+                                    const int64_t* t, const float* sa, const float* s1, const float* w,
+                                    const float* coef, int T, int N, int per, float vlb_weight, const float* dloss,
+                                    float* loss, float* dout, float* ws, void* stream) {
+  return hybrid_launch("dmc_hybrid_objective", pred_type, type, out, x0, noise, t, sa, s1, w, nullptr, coef, T, N, per,
+                       vlb_weight, dloss, loss, nullptr, dout, ws, stream);
+}
+
+extern "C" int dmc_hybrid_objective_is(int pred_type, int type, const float* out, const float* x0, const float* noise,
+                                       const int64_t* t, const float* sa, const float* s1, const float* w,
+                                       const float* iw, const float* coef, int T, int N, int per, float vlb_weight,
+                                       const float* dloss, float* loss, float* row_loss, float* dout, float* ws,
+                                       void* stream) {
+  return hybrid_launch("dmc_hybrid_objective_is", pred_type, type, out, x0, noise, t, sa, s1, w, iw, coef, T, N, per,
+                       vlb_weight, dloss, loss, row_loss, dout, ws, stream);
 }
 
 extern "C" int dmc_vlb_step_learned(const float* x0, const float* x_t, const float* pred, long pred_stride,

@@ -69,13 +69,15 @@ class DDIM(ObjectiveMixin, EditMixin, LikelihoodMixin):
                           self._tab("sqrt_alphas_cumprod", dev), self._tab("sqrt_one_minus_alphas_cumprod", dev))
 
     def p_losses(self, model, x_start, t, y=None, noise=None, loss_type='l2', snr_gamma=None, vlb_weight=None,
-                 return_parts=False):
-        """As DDPM.p_losses (snr_gamma, the v target and the hybrid loss of learned_range are not in the reference)."""
+                 return_parts=False, schedule_sampler=None):
+        """As DDPM.p_losses (snr_gamma, the v target, the hybrid loss of learned_range and schedule_sampler are not in
+        the reference)."""
         if noise is None:
             noise = torch.randn_like(x_start)
         x_noisy = self.q_sample(x_start, t, noise)
         predicted_noise = model(x_noisy, t, y)
-        return self._losses(predicted_noise, x_start, noise, t, loss_type, snr_gamma, vlb_weight, return_parts)
+        return self._losses(predicted_noise, x_start, noise, t, loss_type, snr_gamma, vlb_weight, return_parts,
+                            schedule_sampler)
 
     def _extract(self, a, t, x_shape):
         batch_size = t.shape[0]

@@ -28,6 +28,11 @@ the prediction and the log-variance interpolation v:
   p_sample / mean     -> dmc_ddpm_step_learned (both halves of the model output read in place, the model's own sigma)
   calc_bpd 'learned'  -> dmc_vlb_step_learned
 With the default 'fixed' nothing new is launched.
+p_losses(schedule_sampler=...) (not in the reference; arXiv:2102.09672 §3.3, resample.py) weights each sample by the
+sampler's importance weight and feeds its loss history:
+  any loss            -> dmc_objective_is / dmc_hybrid_objective_is (the same kernels with iw[t] and the per-sample loss), via
+                         _ObjectiveISFn / _HybridISFn, then dmc_ts_history_update
+Without a sampler nothing new is launched.
 """
 import numpy as np
 import torch
@@ -120,6 +125,51 @@ class _HybridFn(torch.autograd.Function):
         return (dout,) + (None,) * 10
 
 
+class _ObjectiveISFn(torch.autograd.Function):
+    """_ObjectiveFn under a schedule sampler (dmc_objective_is): iw is the sampler's [T] importance weights (None: 1).
+    Returns (loss, row_loss); row_loss, each sample's own loss before iw, carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, pred, x0, noise, t, sa, s1, w, iw, pred_type, loss_type):
+        pred = pred.contiguous().float()
+        ctx.save_for_backward(pred, x0, noise, t, sa, s1, w, iw)
+        ctx.types = (pred_type, loss_type)
+        loss, row, _ = K.objective_is(pred_type, loss_type, pred, x0, noise, t, sa, s1, w, iw, grad=False)
+        ctx.mark_non_differentiable(row)
+        return loss, row
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        pred, x0, noise, t, sa, s1, w, iw = ctx.saved_tensors
+        _, _, dpred = K.objective_is(*ctx.types, pred, x0, noise, t, sa, s1, w, iw, dloss=g.contiguous().float(),
+                                     row_loss=False)
+        return (dpred,) + (None,) * 9
+
+
+class _HybridISFn(torch.autograd.Function):
+    """_HybridFn under a schedule sampler (dmc_hybrid_objective_is). Returns (total, simple, vlb, row_loss); only the
+    total carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, out, x0, noise, t, sa, s1, w, iw, coef, pred_type, loss_type, vlb_weight):
+        out = out.contiguous().float()
+        ctx.save_for_backward(out, x0, noise, t, sa, s1, w, iw, coef)
+        ctx.args = (pred_type, loss_type, vlb_weight)
+        loss, row, _ = K.hybrid_objective_is(pred_type, loss_type, out, x0, noise, t, sa, s1, coef, w, iw, vlb_weight,
+                                             grad=False)
+        total, simple, vlb = loss[0], loss[1], loss[2]
+        ctx.mark_non_differentiable(simple, vlb, row)
+        return total, simple, vlb, row
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        out, x0, noise, t, sa, s1, w, iw, coef = ctx.saved_tensors
+        pred_type, loss_type, vlb_weight = ctx.args
+        _, _, dout = K.hybrid_objective_is(pred_type, loss_type, out, x0, noise, t, sa, s1, coef, w, iw, vlb_weight,
+                                           dloss=g.contiguous().float(), row_loss=False)
+        return (dout,) + (None,) * 11
+
+
 class ObjectiveMixin:
     """prediction_type, variance_type, the min-SNR weight tables and the launches they need, shared by DDPM and DDIM
     (and so DPMSolver): both carry sqrt_alphas_cumprod / sqrt_one_minus_alphas_cumprod and _tab()."""
@@ -168,8 +218,11 @@ class ObjectiveMixin:
             return out
         return self._check_out(out, x)[:, :x.shape[1]].contiguous()
 
-    def _losses(self, out, x_start, noise, t, loss_type, snr_gamma, vlb_weight, return_parts):
+    def _losses(self, out, x_start, noise, t, loss_type, snr_gamma, vlb_weight, return_parts, schedule_sampler=None):
         """p_losses after the model call."""
+        if schedule_sampler is not None:
+            return self._sampled_losses(out, x_start, noise, t, loss_type, snr_gamma, vlb_weight, return_parts,
+                                        schedule_sampler)
         if self.variance_type != "learned_range":
             if vlb_weight is not None or return_parts:
                 raise ValueError("vlb_weight and return_parts need variance_type='learned_range'")
@@ -188,6 +241,32 @@ class ObjectiveMixin:
             self._tab("sqrt_alphas_cumprod", dev), self._tab("sqrt_one_minus_alphas_cumprod", dev), w,
             self._lvar_table(dev), self.prediction_type, loss_type, vw)
         return (total, simple, vlb) if return_parts else total
+
+    def _sampled_losses(self, out, x_start, noise, t, loss_type, snr_gamma, vlb_weight, return_parts, sampler):
+        """_losses under a schedule sampler: every objective, the default one included, goes through the _is kernels with
+        the sampler's importance weights, and (when grad is enabled) the per-sample losses feed the sampler's history."""
+        learned = self.variance_type == "learned_range"
+        if not learned and (vlb_weight is not None or return_parts):
+            raise ValueError("vlb_weight and return_parts need variance_type='learned_range'")
+        if loss_type not in ("l1", "l2", "huber"):
+            raise ValueError(f"Unknown loss type: {loss_type}")
+        _require_cuda(out, x_start, noise)
+        dev = out.device
+        w = None if snr_gamma is None else self._snr_weights(snr_gamma, dev)
+        iw = sampler.weight_table()
+        t = t.to(dev).long().contiguous()
+        args = (x_start.contiguous().float(), noise.contiguous().float(), t, self._tab("sqrt_alphas_cumprod", dev),
+                self._tab("sqrt_one_minus_alphas_cumprod", dev), w, iw)
+        if learned:
+            self._check_out(out, x_start)
+            total, simple, vlb, row = _HybridISFn.apply(out, *args, self._lvar_table(dev), self.prediction_type,
+                                                        loss_type, self._vlb_weight(vlb_weight))
+            res = (total, simple, vlb) if return_parts else total
+        else:
+            res, row = _ObjectiveISFn.apply(out, *args, self.prediction_type, loss_type)
+        if torch.is_grad_enabled():
+            sampler.update_with_local_losses(t, row)
+        return res
 
     def _snr_weights(self, gamma, dev):
         """[T] fp32 device table of min-SNR-gamma weights for the current prediction type, built and uploaded once
@@ -272,16 +351,19 @@ class DDPM(ObjectiveMixin, EditMixin, LikelihoodMixin):
                           self._tab("sqrt_alphas_cumprod", dev), self._tab("sqrt_one_minus_alphas_cumprod", dev))
 
     def p_losses(self, model, x_start, t, y=None, noise=None, loss_type='l2', snr_gamma=None, vlb_weight=None,
-                 return_parts=False):
+                 return_parts=False, schedule_sampler=None):
         """Training loss (diffusion/ddpm.py:106-140). Not in the reference: snr_gamma (min-SNR-gamma weighting) and
         the v target of prediction_type='v', both through dmc_objective; with variance_type='learned_range' the
         hybrid loss L_simple + vlb_weight * L_vlb (arXiv:2102.09672 eq. 16; vlb_weight None: 0.001) through
-        dmc_hybrid_objective, and return_parts=True gives (total, simple, vlb_weight * L_vlb)."""
+        dmc_hybrid_objective, and return_parts=True gives (total, simple, vlb_weight * L_vlb). schedule_sampler: the
+        sampler t was drawn from (resample.py); the loss is then weighted by its importance weights and, when grad is
+        enabled, the per-sample losses enter its history."""
         if noise is None:
             noise = torch.randn_like(x_start)
         x_noisy = self.q_sample(x_start, t, noise)
         predicted_noise = model(x_noisy, t, y)
-        return self._losses(predicted_noise, x_start, noise, t, loss_type, snr_gamma, vlb_weight, return_parts)
+        return self._losses(predicted_noise, x_start, noise, t, loss_type, snr_gamma, vlb_weight, return_parts,
+                            schedule_sampler)
 
     def _extract(self, a, t, x_shape):
         batch_size = t.shape[0]

@@ -670,6 +670,32 @@ def objective(pred_type, loss_type, pred, x0, noise, t, sa, s1, w=None, dloss=No
     per-sample weight w[t] (None: 1), mean over samples of the per-sample means. grad=False is the forward alone.
     Returns (loss, dpred or None); dloss: the upstream gradient, a device scalar; out: the dpred buffer to fill."""
     what = "dmc_objective"
+    code, T, N, loss, dpred, ws = _objective_operands(what, pred_type, loss_type, pred, x0, noise, t, sa, s1, (w,), dloss,
+                                                      grad, out)
+    check(LIB.dmc_objective(code, L.LOSS[loss_type], ptr(pred), ptr(x0), ptr(noise), ptr(t), ptr(sa), ptr(s1), ptr(w),
+                            T, N, pred.numel() // N, ptr(dloss) if grad else None, ptr(loss), ptr(dpred), ptr(ws),
+                            L.stream()), what)
+    return loss, dpred
+
+
+def objective_is(pred_type, loss_type, pred, x0, noise, t, sa, s1, w=None, iw=None, dloss=None, grad=True, out=None,
+                 row_loss=True):
+    """objective under importance-sampled timesteps (dmc_objective_is): iw, the [T] importance weights of ts_sample
+    (None: 1), is each sample's last factor in the loss and the gradient. Returns (loss, row_loss or None, dpred or
+    None); row_loss [N] is each sample's own loss before iw, what ts_history_update takes."""
+    what = "dmc_objective_is"
+    code, T, N, loss, dpred, ws = _objective_operands(what, pred_type, loss_type, pred, x0, noise, t, sa, s1, (w, iw),
+                                                      dloss, grad, out)
+    row = torch.empty(N, dtype=torch.float32, device=pred.device) if row_loss else None
+    check(LIB.dmc_objective_is(code, L.LOSS[loss_type], ptr(pred), ptr(x0), ptr(noise), ptr(t), ptr(sa), ptr(s1), ptr(w),
+                               ptr(iw), T, N, pred.numel() // N, ptr(dloss) if grad else None, ptr(loss), ptr(row),
+                               ptr(dpred), ptr(ws), L.stream()), what)
+    return loss, row, dpred
+
+
+def _objective_operands(what, pred_type, loss_type, pred, x0, noise, t, sa, s1, tabs, dloss, grad, out):
+    """The operand checks and buffers objective and objective_is share: (prediction code, T, N, loss, dpred or None,
+    workspace). tabs: the optional [T] tables beside sa and s1."""
     code = _pred_code(what, pred_type)
     if loss_type not in L.LOSS:
         raise L.DMCError(f"{what}: unknown loss type {loss_type!r}")
@@ -679,7 +705,7 @@ def objective(pred_type, loss_type, pred, x0, noise, t, sa, s1, w=None, dloss=No
     _same(pred, x0, noise, what=what)
     _fp32_contig(what, pred, x0, noise)
     _steps(N, pred.device, t, what=what)
-    T = _tables(what, pred.device, sa, s1, w)
+    T = _tables(what, pred.device, sa, s1, *tabs)
     if t is None or T is None or sa is None or s1 is None:
         raise L.DMCError(f"{what}: needs timesteps and the sqrt_alphas_cumprod / sqrt_one_minus_alphas_cumprod tables")
     dpred = None
@@ -691,10 +717,7 @@ def objective(pred_type, loss_type, pred, x0, noise, t, sa, s1, w=None, dloss=No
         _fp32_contig(what, dpred)
     loss = torch.empty((), dtype=torch.float32, device=pred.device)
     ws = SCRATCH.get(L.OBJECTIVE_MAX_BLOCKS * N * 4, pred.device)
-    check(LIB.dmc_objective(code, L.LOSS[loss_type], ptr(pred), ptr(x0), ptr(noise), ptr(t), ptr(sa), ptr(s1), ptr(w),
-                            T, N, pred.numel() // N, ptr(dloss) if grad else None, ptr(loss), ptr(dpred), ptr(ws),
-                            L.stream()), what)
-    return loss, dpred
+    return code, T, N, loss, dpred, ws
 
 
 def pred_convert(pred_type, x, t, sa, s1, pred, want_x0=True, out=None):
@@ -788,6 +811,32 @@ def hybrid_objective(pred_type, loss_type, out, x0, noise, t, sa, s1, coef, w=No
     [N, 2C, ...], prediction half then v; x0, noise: [N, C, ...]; coef: the [T, 8] table of
     diffusion/_vlb.py learned_coefficients. Returns (loss[3] = {total, simple, vlb}, dout or None)."""
     what = "dmc_hybrid_objective"
+    code, T, N, loss, dout, ws = _hybrid_operands(what, pred_type, loss_type, out, x0, noise, t, sa, s1, coef,
+                                                  {"w": w}, dloss, grad, dout)
+    check(LIB.dmc_hybrid_objective(code, L.LOSS[loss_type], ptr(out), ptr(x0), ptr(noise), ptr(t), ptr(sa), ptr(s1),
+                                   ptr(w), ptr(coef), T, N, x0.numel() // N, float(vlb_weight),
+                                   ptr(dloss) if grad else None, ptr(loss), ptr(dout), ptr(ws), L.stream()), what)
+    return loss, dout
+
+
+def hybrid_objective_is(pred_type, loss_type, out, x0, noise, t, sa, s1, coef, w=None, iw=None, vlb_weight=0.001,
+                        dloss=None, grad=True, dout=None, row_loss=True):
+    """hybrid_objective under importance-sampled timesteps (dmc_hybrid_objective_is), as objective_is. Returns
+    (loss[3], row_loss or None, dout or None); row_loss[n] = simple_n + vlb_weight * vb_n, before iw."""
+    what = "dmc_hybrid_objective_is"
+    code, T, N, loss, dout, ws = _hybrid_operands(what, pred_type, loss_type, out, x0, noise, t, sa, s1, coef,
+                                                  {"w": w, "iw": iw}, dloss, grad, dout)
+    row = torch.empty(N, dtype=torch.float32, device=x0.device) if row_loss else None
+    check(LIB.dmc_hybrid_objective_is(code, L.LOSS[loss_type], ptr(out), ptr(x0), ptr(noise), ptr(t), ptr(sa), ptr(s1),
+                                      ptr(w), ptr(iw), ptr(coef), T, N, x0.numel() // N, float(vlb_weight),
+                                      ptr(dloss) if grad else None, ptr(loss), ptr(row), ptr(dout), ptr(ws),
+                                      L.stream()), what)
+    return loss, row, dout
+
+
+def _hybrid_operands(what, pred_type, loss_type, out, x0, noise, t, sa, s1, coef, tabs, dloss, grad, dout):
+    """The operand checks and buffers hybrid_objective and hybrid_objective_is share: (prediction code, T, N, loss[3],
+    dout or None, workspace). tabs: name -> the optional [T] tables beside sa and s1."""
     code = _pred_code(what, pred_type)
     if loss_type not in L.LOSS:
         raise L.DMCError(f"{what}: unknown loss type {loss_type!r}")
@@ -802,8 +851,10 @@ def hybrid_objective(pred_type, loss_type, out, x0, noise, t, sa, s1, coef, w=No
         raise L.DMCError(f"{what}: needs timesteps")
     _steps(N, dev, t, what=what)
     T = _lvar_coef(what, coef, dev)
-    if _tables(what, dev, sa, s1, w) not in (None, T) or (code == L.PRED["v"] and (sa is None or s1 is None)):
-        raise L.DMCError(f"{what}: sa, s1 and w must be [T = {T}] tables (sa and s1 are needed for v-prediction)")
+    if (_tables(what, dev, sa, s1, *tabs.values()) not in (None, T)
+            or (code == L.PRED["v"] and (sa is None or s1 is None))):
+        names = ", ".join(["sa", "s1"] + list(tabs)[:-1]) + " and " + list(tabs)[-1]
+        raise L.DMCError(f"{what}: {names} must be [T = {T}] tables (sa and s1 are needed for v-prediction)")
     if grad:
         if dloss is None or dloss.numel() != 1 or dloss.dtype != torch.float32 or dloss.device != dev:
             raise L.DMCError(f"{what}: dloss must be one fp32 value on {dev}")
@@ -814,10 +865,56 @@ def hybrid_objective(pred_type, loss_type, out, x0, noise, t, sa, s1, coef, w=No
         dout = None
     loss = torch.empty(3, dtype=torch.float32, device=dev)
     ws = SCRATCH.get(2 * L.OBJECTIVE_MAX_BLOCKS * N * 4, dev)
-    check(LIB.dmc_hybrid_objective(code, L.LOSS[loss_type], ptr(out), ptr(x0), ptr(noise), ptr(t), ptr(sa), ptr(s1),
-                                   ptr(w), ptr(coef), T, N, x0.numel() // N, float(vlb_weight),
-                                   ptr(dloss) if grad else None, ptr(loss), ptr(dout), ptr(ws), L.stream()), what)
-    return loss, dout
+    return code, T, N, loss, dout, ws
+
+
+def _ts_state(what, hist, count):
+    """(T, K) of the loss history: hist fp32 [T, K] and count int32 [T], contiguous, on one device."""
+    if (not hist.is_cuda or hist.dim() != 2 or hist.numel() < 1 or hist.dtype != torch.float32
+            or not hist.is_contiguous() or count.shape != (hist.shape[0],) or count.dtype != torch.int32
+            or count.device != hist.device or not count.is_contiguous()):
+        raise L.DMCError(f"{what}: the history must be a contiguous fp32 [T, K] device tensor with an int32 [T] count "
+                         f"beside it, got {hist.dtype} {tuple(hist.shape)} on {hist.device} and {count.dtype} "
+                         f"{tuple(count.shape)} on {count.device}")
+    return hist.shape
+
+
+def ts_history_update(t, loss, hist, count):
+    """hist[tt][count[tt] % K] = loss[n]; ++count[tt] for n in index order, tt = t[n] clamped into [0, T)
+    (dmc_ts_history_update): the last K losses per timestep, in place, exactly as the sequential loop leaves them."""
+    what = "dmc_ts_history_update"
+    T, K = _ts_state(what, hist, count)
+    N = loss.numel()
+    if N < 1 or loss.dim() != 1 or loss.device != hist.device:
+        raise L.DMCError(f"{what}: loss must be a non-empty [N] tensor on {hist.device}, got {tuple(loss.shape)} on "
+                         f"{loss.device}")
+    _fp32_contig(what, loss)
+    if t is None:
+        raise L.DMCError(f"{what}: needs timesteps")
+    _steps(N, hist.device, t, what=what)
+    check(LIB.dmc_ts_history_update(ptr(t), ptr(loss), N, T, K, ptr(hist), ptr(count), L.stream()), what)
+
+
+def ts_sample(hist, count, uniform_prob, u, out=None):
+    """Loss-second-moment timestep draw in one launch (dmc_ts_sample): p ~ sqrt(mean_k hist^2) mixed with uniform_prob
+    of the uniform distribution (uniform, iw = 1, until every count >= K), iw = 1/(T p), cdf, and t[n] = the smallest i
+    with cdf[i] > u[n] for the caller's draws u in [0, 1). Returns (t int64 [N], p, iw, cdf: fp32 [T]); out: the three
+    [T] buffers to fill."""
+    what = "dmc_ts_sample"
+    T, K = _ts_state(what, hist, count)
+    dev = hist.device
+    if u.dim() != 1 or u.numel() < 1 or u.device != dev:
+        raise L.DMCError(f"{what}: u must be a non-empty [N] tensor on {dev}, got {tuple(u.shape)} on {u.device}")
+    _fp32_contig(what, u)
+    if not 0.0 <= float(uniform_prob) < 1.0:
+        raise L.DMCError(f"{what}: uniform_prob {uniform_prob!r} is not in [0, 1)")
+    p, iw, cdf = out if out is not None else (torch.empty(T, dtype=torch.float32, device=dev) for _ in range(3))
+    if _tables(what, dev, p, iw, cdf) != T:
+        raise L.DMCError(f"{what}: p, iw and cdf must be [T = {T}] tables")
+    t = torch.empty(u.numel(), dtype=torch.long, device=dev)
+    check(LIB.dmc_ts_sample(ptr(hist), ptr(count), T, K, float(uniform_prob), ptr(u), u.numel(), ptr(t), ptr(p), ptr(iw),
+                            ptr(cdf), L.stream()), what)
+    return t, p, iw, cdf
 
 
 def vlb_step_learned(x0, x_t, out, t, coef, clip=True, z_next=None, t_next=None, sa=None, s1=None, x_next=None,

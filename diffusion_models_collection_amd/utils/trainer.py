@@ -287,6 +287,7 @@ class GraphedTrainStep:
         return (os.environ.get("DMC_GRAPH", "1") != "0"
                 and (not trainer.is_distributed or trainer.grad_sync is not None)
                 and trainer._flat is not None and trainer.gradient_accumulation_steps == 1
+                and getattr(trainer, "schedule_sampler", None) is None      # the sampler's two launches run eager
                 and _is_dmc_model(trainer._raw_model))
 
     def _key(self, images, y):
@@ -569,6 +570,12 @@ class DiffusionTrainer:
             self.snr_gamma = check_gamma(self.snr_gamma)
         if self.config.get('prediction_type') is not None:
             self.diffusion.set_prediction_type(self.config['prediction_type'])
+        # not in the reference: 'loss-second-moment' draws t by the loss history (diffusion/resample.py) and runs the
+        # step eager; absent, None or 'uniform' is the reference's torch.randint and nothing else
+        self.schedule_sampler = None
+        if self.config.get('schedule_sampler') not in (None, 'uniform'):
+            from ..diffusion.resample import create_named_schedule_sampler
+            self.schedule_sampler = create_named_schedule_sampler(self.config['schedule_sampler'], self.diffusion)
         self.gradient_accumulation_steps = self.config.get('gradient_accumulation_steps', 1)
         self.save_interval = self.config.get('save_interval', 10)
         self.sample_interval = self.config.get('sample_interval', 5)
@@ -721,13 +728,18 @@ class DiffusionTrainer:
             labels_for_loss = None
         images = images.to(self.device, non_blocking=True)
         batch_size = images.shape[0]
-        t = torch.randint(0, self.diffusion.num_timesteps, (batch_size,), device=self.device).long()
+        if self.schedule_sampler is None:
+            t = torch.randint(0, self.diffusion.num_timesteps, (batch_size,), device=self.device).long()
+        else:
+            t, _ = self.schedule_sampler.sample(batch_size, self.device)
         if self._graph is not None and self._module.training:
             loss = self._graph.step(images, t, labels_for_loss)
             if loss is not None:
                 return loss
         # snr_gamma is passed only when set: a p_losses with the reference's signature keeps working
         extra = {} if self.snr_gamma is None else {'snr_gamma': self.snr_gamma}
+        if self.schedule_sampler is not None:
+            extra['schedule_sampler'] = self.schedule_sampler
         loss = self.diffusion.p_losses(self.model, images, t, labels_for_loss, loss_type=self.loss_type, **extra)
         loss = loss / self.gradient_accumulation_steps
         loss.backward()

@@ -397,6 +397,19 @@ int dmc_objective(int pred_type, int loss_type, const float* pred, const float* 
                   const int64_t* t, const float* sa, const float* s1, const float* w, int T, int N,
                   int per_sample, const float* dloss, float* loss, float* dpred, float* workspace,
                   void* stream);
+/* dmc_objective under importance-sampled timesteps (dmc_ts_sample below): iw: [T] importance weights or NULL for 1,
+ * row_loss: [N] or NULL. The same kernels as dmc_objective, which passes NULL for both.
+ *   row_loss[n] = w[t_n] * (1/per_sample) * sum_i f(target - pred): sample n's own loss BEFORE the importance weight,
+ *                 the value dmc_ts_history_update takes
+ *   loss[0]     = (1/N) sum_n iw[t_n] * row_loss[n], samples in index order
+ *   dpred       = (df/dpred * ((dloss[0] / (float)(N*per_sample)) * w[t_n])) * iw[t_n]: iw is the LAST factor, so dpred
+ *                 is iw[t_n] times dmc_objective's dpred rounded once
+ * iw == NULL or all ones: loss and dpred have dmc_objective's bits. Workspace, determinism and access widths as
+ * dmc_objective; row_loss and iw are accessed element-wise. */
+int dmc_objective_is(int pred_type, int loss_type, const float* pred, const float* x0, const float* noise,
+                     const int64_t* t, const float* sa, const float* s1, const float* w, const float* iw, int T,
+                     int N, int per_sample, const float* dloss, float* loss, float* row_loss, float* dpred,
+                     float* workspace, void* stream);
 /* v-prediction model output -> what the step kernels consume (arXiv:2202.00512 appendix D):
  * eps = s1[t]*x + sa[t]*pred, x0 = sa[t]*x - s1[t]*pred (formed directly: no division by alpha). pred, eps_out,
  * x0_out: [reps*N][per_sample]; row r*N + n pairs with x[n], t[n] (reps = 2: the batched cond / uncond forward of
@@ -461,6 +474,16 @@ int dmc_hybrid_objective(int pred_type, int loss_type, const float* out, const f
                          const int64_t* t, const float* sa, const float* s1, const float* w, const float* coef,
                          int T, int N, int per_sample, float vlb_weight, const float* dloss, float* loss,
                          float* dout, float* workspace, void* stream);
+/* dmc_hybrid_objective under importance-sampled timesteps, as dmc_objective_is: iw: [T] or NULL for 1, row_loss: [N] or
+ * NULL. With simple_n and vb_n sample n's terms of L_simple and of mean_n vb_n:
+ *   row_loss[n] = simple_n + vlb_weight * vb_n          -- before the importance weight
+ *   loss[3]     = {loss[1] + loss[2], (1/N) sum_n iw[t_n]*simple_n, vlb_weight * (1/N) sum_n iw[t_n]*vb_n}
+ *   dout        = dmc_hybrid_objective's dout times iw[t_n] as the last factor, in both halves
+ * iw == NULL or all ones: loss and dout have dmc_hybrid_objective's bits. Workspace and determinism as there. */
+int dmc_hybrid_objective_is(int pred_type, int loss_type, const float* out, const float* x0, const float* noise,
+                            const int64_t* t, const float* sa, const float* s1, const float* w, const float* iw,
+                            const float* coef, int T, int N, int per_sample, float vlb_weight, const float* dloss,
+                            float* loss, float* row_loss, float* dout, float* workspace, void* stream);
 /* dmc_vlb_step with the learned term: pred and v are given as a base pointer and a row stride in floats (the two halves
  * of the model output, read in place). Outputs, the x_next contract, clip and the workspace as dmc_vlb_step. */
 int dmc_vlb_step_learned(const float* x0, const float* x_t, const float* pred, long pred_stride, const float* v,
@@ -475,6 +498,32 @@ int dmc_ddpm_step_learned(const float* x, const float* eps, long eps_stride, con
                           const float* x0_in, const int64_t* t, const float* sqrt_recip_ac,
                           const float* sqrt_recipm1_ac, const float* coef1, const float* coef2, const float* coef,
                           int T, int N, int per_sample, int clip, const float* z, float* out, void* stream);
+
+/* Loss-aware timestep sampling (Nichol & Dhariwal 2021, arXiv:2102.09672 §3.3); not in the reference. The last K losses
+ * seen at each timestep, hist: [T][K] fp32, and the number ever seen, count: [T] int32, live on the device; nothing is
+ * read back. Host restatement: diffusion/_resample.py.
+ *
+ * dmc_ts_history_update: for n = 0..N-1 in index order, tt = t[n] clamped into [0, T):
+ *   hist[tt][count[tt] % K] = loss[n];  ++count[tt]
+ * A ring: row tt holds the multiset of the paper's shift-left buffer once count[tt] >= K ("warm"), and only the multiset
+ * enters the weights. One thread per timestep scans the batch, staged in LDS in chunks (any N), and writes its own row
+ * alone: samples sharing a t land exactly as the sequential loop has them. No atomics, deterministic, no workspace.
+ *
+ * dmc_ts_sample, ONE launch (a single block striding over T; any T >= 1, N >= 1):
+ *   warm = all_t(count[t] >= K);  r_t = sqrt(mean_k hist[t][k]^2);  S = sum_t r_t
+ *   !warm, or S not a positive finite number:  p_t = 1/T, iw_t = 1 exactly, cdf[i] = (i+1)/T
+ *   otherwise  q_t = r_t/S*(1 - uniform_prob) + uniform_prob/T;  p_t = q_t / sum_t q_t;  iw_t = 1/(T*p_t)
+ *   cdf = inclusive prefix sum of p, cdf[T-1] stored as exactly 1
+ *   t_out[n] = the smallest i with cdf[i] > u[n], searched in the fp32 cdf as stored (T-1 if there is none)
+ * u: [N] in [0, 1), the caller's draw (torch.rand): no RNG in the kernel. Squares, means, sqrt, both sums, the
+ * divisions and the scan run in double in a fixed order (per-thread partial sums in index order, then a fixed tree;
+ * every op a separate rounding); p, iw and cdf are each rounded to fp32 once. uniform_prob in [0, 1); with 0 a warm row of
+ * zeros has p_t = 0 and iw_t = +inf, and the strict '>' never draws it except as the fallback T-1. Deterministic, no
+ * atomics, no workspace. */
+int dmc_ts_history_update(const int64_t* t, const float* loss, int N, int T, int K, float* hist, int32_t* count,
+                          void* stream);
+int dmc_ts_sample(const float* hist, const int32_t* count, int T, int K, float uniform_prob, const float* u, int N,
+                  int64_t* t_out, float* p, float* iw, float* cdf, void* stream);
 
 /* DDIM.p_sample update (diffusion/ddim.py:154-208), fused; alpha gathers on device; if any
  * t_next < 0 the reference uses alpha_next = 1 for the whole batch (:176-179), so does this.

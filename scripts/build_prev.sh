@@ -9,9 +9,9 @@ mkdir -p $T/csrc $T/include
 for f in $(git -C $R ls-tree --name-only $REV diffusion_models_collection_amd/csrc/); do git -C $R show $REV:$f > $T/csrc/$(basename $f); done
 for f in $(git -C $R ls-tree --name-only $REV include/); do git -C $R show $REV:$f > $T/include/$(basename $f); done
 O=""
-for s in dmc_conv dmc_wgrad dmc_norm dmc_attn dmc_elem dmc_dit dmc_mamba dmc_data; do
+for s in dmc_conv dmc_wgrad dmc_norm dmc_attn dmc_elem dmc_dit dmc_mamba dmc_data dmc_resample; do
   [ -f $T/csrc/$s.hip ] || continue   # a revision from before that file
-  X=""; [ $s = dmc_elem ] || [ $s = dmc_data ] && X="-ffp-contract=off"
+  X=""; [ $s = dmc_elem ] || [ $s = dmc_data ] || [ $s = dmc_resample ] && X="-ffp-contract=off"
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wno-unused-function -Wno-unused-variable $X \
     -I $T/include -I $T/csrc -c $T/csrc/$s.hip -o $T/$s.o &
   O="$O $T/$s.o"
