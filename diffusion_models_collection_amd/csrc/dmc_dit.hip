@@ -542,6 +542,7 @@ extern "C" int dmc_ln_mod_bwd(int dtype, const void* dh, int ld_dh, const float*
                               float* dscale, float* dshift, void* workspace, void* stream) {
   DMC_REQUIRE(C % 4 == 0 && C <= 64 * 4 * kMaxV && T % L == 0 && L > 0, "ln_mod_bwd: C %d (<= %d) T %d L %d", C,
               64 * 4 * kMaxV, T, L);
+  DMC_REQUIRE(ld_dh % 4 == 0 && ld_mod % 4 == 0, "ln_mod_bwd: leading dims");
   hipStream_t s = dmc::as_stream(stream);
   const int B = T / L;
   const int S = workspace ? row_splits(B, L) : 1;
@@ -585,6 +586,7 @@ extern "C" int dmc_ln_affine_mod_bwd(int dtype, const void* dh, int ld_dh, const
                                      float* dgamma, float* dbeta, void* workspace, void* stream) {
   DMC_REQUIRE(C % 4 == 0 && C <= 64 * 4 * kMaxV && T % L == 0 && L > 0, "ln_affine_mod_bwd: C %d (<= %d) T %d L %d", C,
               64 * 4 * kMaxV, T, L);
+  DMC_REQUIRE(ld_dh % 4 == 0 && ld_mod % 4 == 0, "ln_affine_mod_bwd: leading dims");
   DMC_REQUIRE(gamma && beta && dgamma && dbeta, "ln_affine_mod_bwd: gamma / beta and their gradients");
   hipStream_t s = dmc::as_stream(stream);
   const int B = T / L;
@@ -607,6 +609,7 @@ extern "C" int dmc_gate_bwd(int dtype, const float* dy, const void* br, int ld_b
                             float drop_scale, void* dbr, int ld_dbr, float* dgate, void* workspace, void* stream) {
   DMC_REQUIRE(C % 4 == 0 && C <= 64 * 4 * kMaxV && T % L == 0 && L > 0, "gate_bwd: C %d (<= %d) T %d L %d", C,
               64 * 4 * kMaxV, T, L);
+  DMC_REQUIRE(ld_br % 4 == 0 && ld_dbr % 4 == 0 && ld_mod % 4 == 0, "gate_bwd: leading dims");
   const Drop d = make_drop(drop_seed, drop_seed_base, drop_thresh, drop_scale);
   hipStream_t s = dmc::as_stream(stream);
   const int B = T / L;
@@ -629,6 +632,7 @@ extern "C" int dmc_gate_bwd_bias(int dtype, const float* dy, const void* br, int
                                  float* dsum, float* dbias, void* workspace, void* stream) {
   DMC_REQUIRE(C % 4 == 0 && C <= 64 * 4 * kMaxV && T % L == 0 && L > 0, "gate_bwd_bias: C %d (<= %d) T %d L %d", C,
               64 * 4 * kMaxV, T, L);
+  DMC_REQUIRE(ld_br % 4 == 0 && ld_dbr % 4 == 0 && ld_mod % 4 == 0, "gate_bwd_bias: leading dims");
   DMC_REQUIRE(dsum && dbias, "gate_bwd_bias: dsum / dbias");
   const Drop d = make_drop(drop_seed, drop_seed_base, drop_thresh, drop_scale);
   hipStream_t s = dmc::as_stream(stream);

@@ -620,6 +620,8 @@ int dmc_add(int dtype, void* y, const void* x, long n, void* stream);
 /* ---- DiT backbone (models/dit.py of the reference; dmc_dit.hip) ----------------------------------------------
  * Token rows [T = B*L][C]; the residual stream x is fp32, GEMM operands (h, branch) are in `dtype`.
  * Modulation vectors (shift / scale / gate) are rows of the stacked adaLN GEMM output [B][ld_mod].
+ * C % 4 == 0, C <= 2048, T % L == 0 and every pitch (ld_br, ld_h, ld_dh, ld_dbr, ld_mod) a multiple of 4 (8- and 16-byte
+ * accesses), in the forward and the backward entry points alike: anything else is refused before a launch.
  * ln_mod_fwd: DiTBlock.forward (dit.py:113-130): x_new = x + gate * dropout(br) when br != NULL (x_out = x_new),
  *   then h = LayerNorm(x_new; eps, no affine) * (1 + scale) + shift; saves the row mean / rstd.
  * ln_mod_bwd: dx += d/dx of that LayerNorm + modulation for upstream dh; dscale / dshift = sums over each image's
