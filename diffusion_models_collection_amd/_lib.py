@@ -53,9 +53,10 @@ class ConvDesc(ctypes.Structure):
 class ConvPlan(ctypes.Structure):
     """include/dmc.h dmc_conv_plan"""
     _fields_ = [("family", _c_int), ("grid", ctypes.c_uint * 3), ("block", _c_int), ("splits", _c_int),
-                ("gn_part", _c_int), ("fused_prologue", _c_int), ("ws_bytes", _c_size)]
+                ("gn_part", _c_int), ("fused_prologue", _c_int), ("ws_bytes", _c_size), ("whole_k", _c_int)]
 
 
+WK_64X128, WK_64X64 = 1, 2   # include/dmc.h DMC_WK_* (ConvPlan.whole_k)
 # include/dmc.h DMC_CONV_* (by code) and DMC_GN_PART_*
 CONV_FAMILIES = ("none", "nin_halo", "nout_halo", "narrow_in", "narrow_out", "img", "gemm1x1", "halo", "glds", "reg")
 GN_PART_NONE, GN_PART_KERNEL, GN_PART_SPLITK, GN_PART_PASS = 0, 1, 2, 3

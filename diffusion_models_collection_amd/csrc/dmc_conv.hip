@@ -564,18 +564,21 @@ __host__ __device__ inline bool reg_epi_ok(const ConvK& a) {
          a.act == DMC_ACT_NONE && (a.Cout & 127) == 0 && (a.ldy1 & 7) == 0 &&
          (!a.resid || (a.ld_res & 7) == 0) && (a.M & 127) == 0 && (!a.gst || a.OHW % 64 == 0);
 }
-template <bool CLS = false>
-DMC_DEV void reg_epilogue(const ConvK& a, v4f (&acc)[4][4], int m0, int n0, int wm, int wn, int par = 0) {
-  // Stores and residual loads are 16 bytes: the lane pair (fh, fh ^ 1) holds the two 4-channel halves of one
-  // 8-channel chunk, so for each pair of pixel fragments (j0, j1) one xor-16 exchange of 2 dwords gives the even
-  // lane the whole chunk of pixel j0 and the odd lane that of pixel j1 (8-byte stores are store-issue bound).
-  const int lane = threadIdx.x & 63, fr = lane & 15, fh = lane >> 4;
-  const bool odd = fh & 1;
-  // every global operand of the epilogue (residual chunks, bias and time-embedding rows) is loaded up front: issued
-  // between the output stores, each load waited for its own round trip (the stores may alias them) -- eight to
-  // twelve serialised L2/HBM latencies per tile (the 32x32 conv's epilogue took a third of the kernel)
+// The epilogue's global operands of one wave: the residual chunks, the bias and the first image's time-embedding row.
+struct RegEpiOps {
   v4i rra[4][2];
   v4f ba[4], eva[4];
+};
+// every global operand of the epilogue (residual chunks, bias and time-embedding rows) is loaded up front: issued
+// between the output stores, each load waited for its own round trip (the stores may alias them) -- eight to
+// twelve serialised L2/HBM latencies per tile (the 32x32 conv's epilogue took a third of the kernel)
+// ADDVEC = false: the caller's planner admits no time-embedding rows (no registers held for them, no branch).
+template <bool CLS = false, bool ADDVEC = true>
+DMC_DEV void reg_epilogue_loads(const ConvK& a, RegEpiOps& e, int m0, int n0, int wm, int wn, int par = 0) {
+  const int lane = threadIdx.x & 63, fr = lane & 15, fh = lane >> 4;
+  const bool odd = fh & 1;
+  v4i (&rra)[4][2] = e.rra;
+  v4f (&ba)[4] = e.ba, (&eva)[4] = e.eva;
   const int img0 = (m0 + wm * 64) / a.OHW;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -591,8 +594,22 @@ DMC_DEV void reg_epilogue(const ConvK& a, v4f (&acc)[4][4], int m0, int n0, int 
       }
     }
     ba[i] = a.bias ? *(const v4f*)(a.bias + co) : v4f{0.f, 0.f, 0.f, 0.f};
-    eva[i] = a.addvec ? *(const v4f*)(a.addvec + (size_t)img0 * a.ld_add + co) : v4f{0.f, 0.f, 0.f, 0.f};
+    eva[i] = ADDVEC && a.addvec ? *(const v4f*)(a.addvec + (size_t)img0 * a.ld_add + co) : v4f{0.f, 0.f, 0.f, 0.f};
   }
+}
+// The arithmetic, the stores and the partials, from operands loaded by reg_epilogue_loads. y / ldy / cbase: the output
+// the wave's 64 channels go to (channel cbase of the conv is its column 0).
+template <bool CLS = false, bool ADDVEC = true>
+DMC_DEV void reg_epilogue_finish(const ConvK& a, v4f (&acc)[4][4], const RegEpiOps& e, int m0, int n0, int wm, int wn,
+                                 int par, char* y, int ldy, int cbase) {
+  // Stores and residual loads are 16 bytes: the lane pair (fh, fh ^ 1) holds the two 4-channel halves of one
+  // 8-channel chunk, so for each pair of pixel fragments (j0, j1) one xor-16 exchange of 2 dwords gives the even
+  // lane the whole chunk of pixel j0 and the odd lane that of pixel j1 (8-byte stores are store-issue bound).
+  const int lane = threadIdx.x & 63, fr = lane & 15, fh = lane >> 4;
+  const bool odd = fh & 1;
+  const v4i (&rra)[4][2] = e.rra;
+  const v4f (&ba)[4] = e.ba, (&eva)[4] = e.eva;
+  const int img0 = (m0 + wm * 64) / a.OHW;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int co = n0 + wn * 64 + i * 16 + fh * 4;
@@ -614,7 +631,7 @@ DMC_DEV void reg_epilogue(const ConvK& a, v4f (&acc)[4][4], int m0, int n0, int 
         const int j = 2 * jp + h;
         const int px = m0 + wm * 64 + j * 16 + fr;
         v4f v = acc[i][j] + b;
-        if (a.addvec) {
+        if (ADDVEC && a.addvec) {
           const int n = px / a.OHW;
           if (n != nimg) { nimg = n; ev = *(const v4f*)(a.addvec + (size_t)n * a.ld_add + co); }
           v = v + ev;
@@ -652,7 +669,7 @@ DMC_DEV void reg_epilogue(const ConvK& a, v4f (&acc)[4][4], int m0, int n0, int 
       else { outv[0] = recv[0]; outv[1] = recv[1]; outv[2] = o[1][0]; outv[3] = o[1][1]; }
       const int pcs = m0 + wm * 64 + (2 * jp + (odd ? 1 : 0)) * 16 + fr;
       const int pxs = CLS ? cls_out_pixel(a, par, pcs) : pcs;
-      *(v4i*)(a.y1 + ((size_t)pxs * a.ldy1 + cc) * 2) = outv;
+      *(v4i*)(y + ((size_t)pxs * ldy + (cc - cbase)) * 2) = outv;
     }
     if (a.gst) {
       float cnt = 16.f;
@@ -670,6 +687,12 @@ DMC_DEV void reg_epilogue(const ConvK& a, v4f (&acc)[4][4], int m0, int n0, int 
       }
     }
   }
+}
+template <bool CLS = false>
+DMC_DEV void reg_epilogue(const ConvK& a, v4f (&acc)[4][4], int m0, int n0, int wm, int wn, int par = 0) {
+  RegEpiOps e;
+  reg_epilogue_loads<CLS>(a, e, m0, n0, wm, wn, par);
+  reg_epilogue_finish<CLS>(a, acc, e, m0, n0, wm, wn, par, a.y1, a.ldy1, 0);
 }
 
 // BUF = true: all operands through buffer resources (raw_ptr_buffer_load_lds), zero padding by the
@@ -1031,6 +1054,205 @@ __global__ __launch_bounds__(256, NS <= 2 ? 2 : 1) void gemm1x1_persist_kernel(C
       __builtin_amdgcn_sched_barrier(0);
     }
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Whole-K form of the 1x1 GEMM, for the problems of at most 128 tiles of 128x128 (the 8x8 and 4x4 maps at B = 128: the
+// attention qkv / proj convs, the 1x1 shortcuts, their input gradients). There the kernels above are a chain of
+// dependent global round trips -- the bias, then one K stage at a time behind a block barrier: 1 + Kc/64 of them --
+// while no launch moves more than 3 us of HBM or MFMA time. Here a block owns ONE output tile and keeps the tile's
+// whole K in LDS, as NSLOT consecutive 64-channel stages in the ring's layout and swizzle (glds_issue_buf and the
+// fragment reads as they are): the epilogue's operands (bias, residual chunks) and every stage's DMA are issued up
+// front, with no drain between them, and stage s is consumed behind a vmcnt wait counted from the wave's issue order
+// plus the block barrier that other waves' DMA data needs. A K of more than NSLOT stages (K = 768 at the 64x128 tile)
+// refills the earliest slots behind that barrier: a deep ring, not a second kernel.
+// Tile = (64 WM pixels) x (64 WN channels), one 64x64 wave tile per wave: 64x128 and 64x64, so that a 4x4 map still
+// fills the CUs (the planner picks the shape: gemm1x1_wk_tile; a 128x128 tile of four waves measured no faster than
+// the persistent GEMM on the one class it would take, and is not instantiated). A conv with a split-K plan takes gemm1x1_wholek_runs_kernel below.
+// Epilogue from the accumulators (reg_epilogue's arithmetic, stores, fold and tree: the same outputs and GroupNorm
+// partials as conv_fwd_glds_kernel's), each side of a split output through its own base.
+template <int WM, int WN, int NSLOT>
+__global__ __launch_bounds__(WM * WN * 64) void gemm1x1_wholek_kernel(ConvK a, int NB) {
+  using T = bf16_t;
+  constexpr int NW = WM * WN, BM = 64 * WM, BN = 64 * WN, SB = (BM + BN) * 128;
+  constexpr int AI = BM / 8 / NW, BI = BN / 8 / NW, PER_STAGE = AI + BI;
+  static_assert(NSLOT * SB <= 160 * 1024, "the stages must fit the CU's LDS");
+  __shared__ __attribute__((aligned(16))) char lds[NSLOT * SB];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wm = wave % WM, wn = wave / WM;
+  const int lrow = lane >> 3, lc = (lane & 7) ^ lrow;
+  const int fr = lane & 15, fh = lane >> 4;
+  int mb, nb;
+  xcd_tile(NB, mb, nb);
+  const int m0 = mb * BM, n0 = nb * BN;
+  const int kst = a.Kc / 64;
+
+  // the epilogue's operands first: they return before the stages (vmcnt counts in issue order), so the stage waits
+  // below need not count them, and the epilogue finds them landed
+  RegEpiOps eo;
+  reg_epilogue_loads<false, false>(a, eo, m0, n0, wm, wn);
+  asm volatile("" ::: "memory");
+  unsigned o1[AI], o2[AI], ob[BI];
+#pragma unroll
+  for (int j = 0; j < AI; ++j) {
+    const unsigned pix = (unsigned)(m0 + (wave * AI + j) * 8 + lrow);
+    o1[j] = (pix * a.ld1 + lc * 8) * 2u;
+    o2[j] = (pix * a.ld2 + lc * 8) * 2u;
+  }
+#pragma unroll
+  for (int j = 0; j < BI; ++j) {
+    const unsigned co = (unsigned)(n0 + (wave * BI + j) * 8 + lrow);
+    ob[j] = (co * a.Kc + lc * 8) * 2u;
+  }
+  auto issue = [&](int S) {
+    glds_issue_buf<AI, BI, BM>(a, lds + (S % NSLOT) * SB, S * 64, (unsigned)S * 128u, wave, o1, o2, ob);
+  };
+  int issued = 0;
+  for (; issued < NSLOT && issued < kst; ++issued) issue(issued);
+
+  v4f acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = v4f{0.f, 0.f, 0.f, 0.f};
+  for (int s = 0; s < kst; ++s) {
+    // stage s has landed once at most the stages issued after it are outstanding
+    wait_vm_upto40((issued - s - 1) * PER_STAGE);
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("" ::: "memory");
+    // every wave has finished reading stage s-1's slot: refill it with the next stage beyond the LDS budget
+    if (s >= 1 && issued < kst) { issue(issued); ++issued; }
+    const char* A = lds + (s % NSLOT) * SB;
+    const char* B = A + BM * 128;
+    v4i fa[2][4], fb[2][4];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const int chunk = ks * 4 + fh;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int r = wn * 64 + i * 16 + fr;
+        fa[ks][i] = *(const v4i*)(B + r * 128 + ((chunk ^ (r & 7)) << 4));
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int r = wm * 64 + j * 16 + fr;
+        fb[ks][j] = *(const v4i*)(A + r * 128 + ((chunk ^ (r & 7)) << 4));
+      }
+    }
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = mma16<T>(acc[i][j], fa[ks][i], fb[ks][j]);
+    __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
+#pragma unroll
+    for (int g = 0; g < 8; ++g) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+    }
+    __builtin_amdgcn_sched_group_barrier(0x008, 16, 0);
+  }
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  // a split output has whole 128-channel tiles on each side, so a wave's 64 channels lie on one
+  const bool second = n0 + wn * 64 >= a.Csplit;
+  reg_epilogue_finish<false, false>(a, acc, eo, m0, n0, wm, wn, 0, second ? a.y2 : a.y1, second ? a.ldy2 : a.ldy1,
+                      second ? a.Csplit : 0);
+}
+
+// The whole-K form of a conv with a split-K plan (plan_glds: NR runs of `per` K stages, summed in ascending order by
+// conv_splitk_epilogue_kernel): one 64x64 tile per block, ONE WAVE PER RUN. Wave r accumulates run r from zero
+// through a ring of its own -- it consumes only what it loaded itself, so its K loop has counted vmcnt waits and no
+// block barrier, and the runs' MFMA chains go to different SIMDs as the split-K blocks went to different CUs. The
+// waves then park their sums in their (consumed) rings and wave 0 adds them in ascending order and runs the epilogue:
+// the bits of the split-K plan, without the slab and its reduction launch.
+template <int NR>
+__global__ __launch_bounds__(NR * 64) void gemm1x1_wholek_runs_kernel(ConvK a, int NB, int per) {
+  using T = bf16_t;
+  constexpr int SB = (64 + 64) * 128, NSLOT = NR == 2 ? 4 : NR == 3 ? 3 : 2, PER_STAGE = 16;
+  static_assert(NR * NSLOT * SB <= 160 * 1024 && NSLOT * SB >= 64 * 64 * 4, "rings fit the LDS, a ring holds a tile of sums");
+  __shared__ __attribute__((aligned(16))) char lds[NR * NSLOT * SB];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lrow = lane >> 3, lc = (lane & 7) ^ lrow;
+  const int fr = lane & 15, fh = lane >> 4;
+  int mb, nb;
+  xcd_tile(NB, mb, nb);
+  const int m0 = mb * 64, n0 = nb * 64;
+  const int kst = a.Kc / 64, s_begin = wave * per, ns = min(kst, s_begin + per) - s_begin;
+  char* const ring = lds + wave * NSLOT * SB;
+
+  RegEpiOps eo;
+  if (wave == 0) reg_epilogue_loads<false, false>(a, eo, m0, n0, 0, 0);
+  asm volatile("" ::: "memory");
+  unsigned o1[8], o2[8], ob[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const unsigned pix = (unsigned)(m0 + j * 8 + lrow), co = (unsigned)(n0 + j * 8 + lrow);
+    o1[j] = (pix * a.ld1 + lc * 8) * 2u;
+    o2[j] = (pix * a.ld2 + lc * 8) * 2u;
+    ob[j] = (co * a.Kc + lc * 8) * 2u;
+  }
+  auto issue = [&](int S) {   // the wave's stage S: all 64 + 64 rows (glds_issue_buf's wave 0 of a one-wave tile)
+    glds_issue_buf<8, 8, 64>(a, ring + (S % NSLOT) * SB, (s_begin + S) * 64, (unsigned)(s_begin + S) * 128u, 0, o1, o2, ob);
+  };
+  int issued = 0;
+  for (; issued < NSLOT && issued < ns; ++issued) issue(issued);
+  v4f acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = v4f{0.f, 0.f, 0.f, 0.f};
+  for (int s = 0; s < ns; ++s) {
+    wait_vm_upto40((issued - s - 1) * PER_STAGE);
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    // stage s-1's fragments are in registers (its MFMAs are issued above): its slot takes the next stage
+    if (s >= 1 && issued < ns) { issue(issued); ++issued; }
+    const char* A = ring + (s % NSLOT) * SB;
+    const char* B = A + 64 * 128;
+    v4i fa[2][4], fb[2][4];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const int chunk = ks * 4 + fh;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int r = i * 16 + fr;
+        fa[ks][i] = *(const v4i*)(B + r * 128 + ((chunk ^ (r & 7)) << 4));
+        fb[ks][i] = *(const v4i*)(A + r * 128 + ((chunk ^ (r & 7)) << 4));
+      }
+    }
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = mma16<T>(acc[i][j], fa[ks][i], fb[ks][j]);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  asm volatile("" ::: "memory");
+  if (wave != 0) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) *(v4f*)(ring + ((i * 4 + j) * 64 + lane) * 16) = acc[i][j];
+  }
+  __syncthreads();
+  if (wave != 0) return;
+#pragma unroll
+  for (int r = 1; r < NR; ++r)
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = acc[i][j] + *(const v4f*)(lds + r * NSLOT * SB + ((i * 4 + j) * 64 + lane) * 16);
+  const bool second = n0 >= a.Csplit;
+  reg_epilogue_finish<false, false>(a, acc, eo, m0, n0, 0, 0, 0, second ? a.y2 : a.y1, second ? a.ldy2 : a.ldy1,
+                                    second ? a.Csplit : 0);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2381,19 +2603,37 @@ __global__ __launch_bounds__(256) void gn_part_kernel(const char* y, int ldy, in
 
 // The persistent 1x1 GEMM applies (bf16 1x1 stride-1, 64-aligned channel sources, plain bias epilogue, whole
 // 128x128 tiles, enough tiles to give every CU one block): returns the tiles per block, or 0.
-int gemm1x1_plan(const ConvK& k) {
+bool gemm1x1_ok(const ConvK& k) {
   if (k.dtype_bytes != 2 || k.ntaps != 1 || k.stride != 1 || k.mode != DMC_MODE_NORMAL || k.tdy0 || k.tdx0 ||
       k.H != k.OH || k.W != k.OW || k.prologue != DMC_PRO_NONE || !dma_operands_ok(k))
-    return 0;
+    return false;
   if (k.addvec || (k.resid && (k.ld_res & 3)) || k.silu_pre || k.act != DMC_ACT_NONE || k.out_f32 || k.out_nchw ||
       (k.ldy1 & 3) || k.M % 128 || k.Cout % 128 || k.Cout > 1024)
-    return 0;
+    return false;
   // a split output: whole 128-channel tiles on each side, no residual (the accumulate form is single-output)
-  if (k.Csplit != k.Cout && (k.Csplit % 128 || (k.ldy2 & 3) || !k.y2 || k.resid)) return 0;
+  if (k.Csplit != k.Cout && (k.Csplit % 128 || (k.ldy2 & 3) || !k.y2 || k.resid)) return false;
+  return true;
+}
+int gemm1x1_plan(const ConvK& k) {
+  if (!gemm1x1_ok(k)) return 0;
   const long ntiles = (long)(k.M / 128) * (k.Cout / 128);
   if (ntiles < 128) return 0;
   const long blocks = 512;   // the 2-slot ring, two blocks per CU (the 4-slot one-block form: +1 % only, round 4)
   return (int)((ntiles + blocks - 1) / blocks);
+}
+
+// The whole-K form of the 1x1 GEMM (gemm1x1_wholek_kernel) applies: the persistent GEMM's predicates with the 16-byte
+// epilogue's alignment, at least two K stages (one stage has no chain to shorten) and at most one 128x128 tile per CU.
+// Returns the tile, DMC_WK_*, or 0 -- 64x64 where that gives at most 256 blocks, one per CU, else 64x128 under the
+// same bound: the smaller tile puts more CUs on a small problem. Beyond that (more than 128 tiles of 128x128) the
+// persistent GEMM keeps the conv: a 128x128 whole-K tile measured no faster than it (DESIGN.md "Whole-K 1x1 GEMM").
+int gemm1x1_wk_tile(const ConvK& k) {
+  if (!gemm1x1_ok(k)) return 0;
+  if ((k.ldy1 & 7) || (k.resid && (k.ld_res & 7)) || (k.Csplit != k.Cout && (k.ldy2 & 7))) return 0;
+  if (k.Kc < 128 || (long)(k.M / 128) * (k.Cout / 128) > 256) return 0;
+  if ((long)(k.M / 64) * (k.Cout / 64) <= 256) return DMC_WK_64X64;
+  if ((long)(k.M / 64) * (k.Cout / 128) <= 256) return DMC_WK_64X128;
+  return 0;
 }
 
 // Everything dmc_conv2d decides before it launches, decided once: launch_conv runs it, the queries
@@ -2406,6 +2646,7 @@ struct ConvPlan {
   int npl = 0;                  // halo'd narrow-out: 64-channel source planes
   int bn = 0;                   // small-map: channel tile
   int tpb = 0;                  // persistent GEMM: tiles per block
+  int wk = 0, wk_runs = 0, wk_per = 0;   // whole-K 1x1 GEMM: tile (DMC_WK_*, 0: not this form); a split-K plan's runs, stages per run
   int wm = 2, stages = 3;       // LDS-DMA: 64-pixel wave rows per tile (2: 128 pixels, 1: 64) and ring depth
   bool buf = false;             // LDS-DMA: buffer-resource (true) or plain (false) operand addressing
   bool cls = false;             // LDS-DMA: the four parity classes of a folded resampling conv over grid.z
@@ -2494,6 +2735,32 @@ ConvPlan plan_conv(const ConvK& k, bool want_gn_part, size_t ws_avail) {
     p.family = DMC_CONV_IMG; p.bn = img_bn;
     p.grid = dim3(k.M / (k.OH == 8 ? 256 : 128) * (k.Cout / img_bn));
     return p;
+  }
+  // The whole-K form of the 1x1 GEMM (DMC_GEMM1X1_WK) takes a small 1x1 conv from whichever plan follows -- the
+  // persistent GEMM, the LDS-DMA kernel or its split-K -- and keeps that plan's bits: a split-K plan of up to 4 runs
+  // goes to one wave per run on the 64x64 tile (gemm1x1_wholek_runs_kernel), and a conv whose partials come from the
+  // epilogue is taken only where that is reg_epilogue on the 128-row tile, whose fold and tree the form runs per wave.
+  // Partials from the 64-row tile's LDS-staged epilogue or from the split-K reduction keep their kernel.
+  if (dmc::opt(dmc::OPT_GEMM1X1) && dmc::opt(dmc::OPT_GEMM1X1_WK) && glds_path && buf && (p.wk = gemm1x1_wk_tile(k)) != 0) {
+    const bool persist = !epi && !skgn && gemm1x1_plan(k) != 0;
+    const bool split = !persist && gp.splits > 1 && ws_avail >= gp.ws && !no_splitk;
+    static float gst_requested;
+    ConvK kg = k;
+    kg.gst = &gst_requested;   // reg_epi_ok as the launch with partials evaluates it
+    if ((split && (want_gn_part || p.wk != DMC_WK_64X64 || gp.splits > 4)) ||
+        (epi && (gp.splits > 1 || gp.cfg == 2 || !reg_epi_ok(kg))))
+      p.wk = 0;
+    // against the persistent GEMM the form wins from K = 512 on (9 and more round trips in that kernel's chain); at
+    // K = 256 the two measured the same (DESIGN.md "Whole-K 1x1 GEMM"), and the persistent GEMM keeps the conv
+    if (persist && k.Kc < 512) p.wk = 0;
+    if (p.wk) {
+      p.family = DMC_CONV_GEMM1X1;
+      if (split) { p.wk_runs = gp.splits; p.wk_per = gp.per; }
+      const int bn = p.wk == DMC_WK_64X64 ? 64 : 128;
+      p.block = split ? 64 * gp.splits : bn;
+      p.grid = dim3((k.M / 64) * (k.Cout / bn));
+      return p;
+    }
   }
   // a conv asked for partials stays off the persistent GEMM (which has no such epilogue) while either epilogue
   // form is armed
@@ -2617,6 +2884,14 @@ int launch_conv(const ConvK& k, const ConvPlan& p, float* part, hipStream_t s) {
       }
       break;
     case DMC_CONV_GEMM1X1: {
+      if (p.wk) {   // slots: as many 64-channel stages as the tile's LDS holds
+        if (p.wk_runs == 2) gemm1x1_wholek_runs_kernel<2><<<g, 128, 0, s>>>(k, k.Cout / 64, p.wk_per);
+        else if (p.wk_runs == 3) gemm1x1_wholek_runs_kernel<3><<<g, 192, 0, s>>>(k, k.Cout / 64, p.wk_per);
+        else if (p.wk_runs == 4) gemm1x1_wholek_runs_kernel<4><<<g, 256, 0, s>>>(k, k.Cout / 64, p.wk_per);
+        else if (p.wk == DMC_WK_64X128) gemm1x1_wholek_kernel<1, 2, 6><<<g, 128, 0, s>>>(k, k.Cout / 128);
+        else gemm1x1_wholek_kernel<1, 1, 8><<<g, 64, 0, s>>>(k, k.Cout / 64);
+        break;
+      }
       const int NB = k.Cout / 128, ntiles = (k.M / 128) * NB;
       gemm1x1_persist_kernel<2><<<g, 256, 0, s>>>(k, ntiles, NB, p.tpb);
       break;
@@ -2740,6 +3015,7 @@ extern "C" int dmc_conv2d_plan(const dmc_conv_desc* d, size_t ws_bytes, dmc_conv
   out->gn_part = p.gn;
   out->fused_prologue = p.fused_pro;
   out->ws_bytes = p.ws_report;
+  out->whole_k = p.wk;
   return 0;
 }
 

@@ -1160,8 +1160,7 @@ int gn_silu_bwd_impl(int dtype, const void* g, int ld_g, const void* x1, const v
   // the one-pass fused kernel when a channel slice's rows fit NR <= DMC_GN_BWD_FUSED (<= 4) chunks per thread
   // (S <= 8 channel slices of whole groups per sample, N*S >= 256 blocks to fill the chip)
   const int fused_max = (int)dmc::opt(dmc::OPT_GN_BWD_FUSED);
-  if (!part && dtype != DMC_F32 && N >= 64 && fused_max > 0 && !dmc::opt(dmc::OPT_GN_BWD_SPLIT) &&
-      HW <= dmc::opt(dmc::OPT_GN_BWD_FUSED_MAXHW)) {
+  if (!part && dtype != DMC_F32 && N >= 64 && fused_max > 0 && !dmc::opt(dmc::OPT_GN_BWD_SPLIT)) {
     // DMC_GN_BWD_NT: threads per block (1024, or 512: two blocks per CU, twice the channel slices)
     const int NT = dmc::opt(dmc::OPT_GN_BWD_NT) == 512 ? 512 : 1024;
     auto rows = [&](int s_) { const int rp = NT / (C / s_ / epc); return rp > 0 ? (HW + rp - 1) / rp : 1 << 30; };

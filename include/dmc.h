@@ -134,7 +134,7 @@ enum { DMC_CONV_NONE = 0,        /* empty problem: nothing is launched */
        DMC_CONV_NARROW_IN = 3,   /* generic narrow-input */
        DMC_CONV_NARROW_OUT = 4,  /* generic narrow-output */
        DMC_CONV_IMG = 5,         /* whole-image small-map 3x3 (4x4 / 8x8) */
-       DMC_CONV_GEMM1X1 = 6,     /* persistent 1x1 GEMM */
+       DMC_CONV_GEMM1X1 = 6,     /* 1x1 GEMM: persistent, or whole-K (dmc_conv_plan.whole_k) */
        DMC_CONV_HALO = 7,        /* 128-pixel halo 3x3 */
        DMC_CONV_GLDS = 8,        /* LDS-DMA implicit GEMM */
        DMC_CONV_REG = 9 };       /* register-staged implicit GEMM */
@@ -150,7 +150,11 @@ typedef struct dmc_conv_plan {
   int gn_part;               /* DMC_GN_PART_* */
   int fused_prologue;        /* what dmc_conv_halo_prologue answers */
   size_t ws_bytes;           /* what dmc_conv2d_workspace answers */
+  int whole_k;               /* DMC_CONV_GEMM1X1: DMC_WK_* when the whole-K form runs (one tile per block, its whole K in
+                              * LDS; with `block` > the tile's 64 threads per 64x64 wave tile: one wave per run of
+                              * the split-K plan it replaces), 0 for the persistent GEMM and every other family */
 } dmc_conv_plan;
+enum { DMC_WK_64X128 = 1, DMC_WK_64X64 = 2 };   /* pixels x channels of the whole-K form's tile */
 int dmc_conv2d_plan(const dmc_conv_desc* d, size_t ws_bytes, dmc_conv_plan* out);
 /* Which output-parity fold (DMC_FOLD_*) dmc_conv2d(d, ..., ws_bytes) can run `d` (written with fold = 0) as:
  *   DMC_FOLD_UP          the forward of models/unet.py:116 (nearest x2, then 3x3 pad 1; mode UPSAMPLE, 9 forward taps):
