@@ -203,6 +203,8 @@ def _load():
                                      _c_p]),
         "dmc_cfg_x0": (_c_int, [_c_p, _c_p, _c_p, _c_f, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_f, _c_p, _c_p,
                                 _c_p]),
+        "dmc_cfg_guide": (_c_int, [_c_int, _c_p, _c_p, _c_long, _c_p, _c_long, _c_f, _c_f, _c_p, _c_p, _c_p, _c_int,
+                                   _c_int, _c_int, _c_f, _c_p, _c_p, _c_p]),
         "dmc_ema_update": (_c_int, [_c_p, _c_int, _c_f, _c_p]),
         "dmc_clip_grad_norm": (_c_int, [_c_p, _c_int, _c_f, _c_p, _c_p, _c_p]),
         "dmc_grad_norm_flat": (_c_int, [_c_p, _c_long, _c_f, _c_p, _c_p, _c_p, _c_p]),

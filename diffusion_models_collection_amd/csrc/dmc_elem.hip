@@ -1049,6 +1049,40 @@ __global__ __launch_bounds__(256) void known_blend_kernel(const float* x, const 
   }
 }
 
+// The threshold tail of the two CFG kernels, by the whole block: sv holds |x0| of the row x0 (padding +inf), written
+// by the caller without a barrier. p in (0,1): s = max(quantile_p |x0|, 1), x0 = clamp(x0, -s, s) / s; else clamp +-1.
+DMC_DEV void cfg_threshold(float* sv, float* x0, int per, int npad, float p) {
+  __syncthreads();
+  if (!(p > 0.f)) {
+    for (int i = threadIdx.x; i < per; i += blockDim.x) x0[i] = fminf(fmaxf(x0[i], -1.0f), 1.0f);
+    return;
+  }
+  // bitonic sort of |x0| (padding +inf sorts last)
+  for (int k = 2; k <= npad; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int i = threadIdx.x; i < npad; i += blockDim.x) {
+        const int ixj = i ^ j;
+        if (ixj > i) {
+          const float a = sv[i], b = sv[ixj];
+          const bool up = (i & k) == 0;
+          if ((a > b) == up) { sv[i] = b; sv[ixj] = a; }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  // torch.quantile(..., interpolation='linear'): rank = q*(n-1) in fp32, lerp
+  const float rank = p * (float)(per - 1);
+  const float lof = floorf(rank);
+  const int lo = (int)lof;
+  const int hi = (int)ceilf(rank);
+  const float w = rank - lof;
+  const float a = sv[lo], b = sv[hi];
+  float s = (w < 0.5f) ? a + w * (b - a) : b - (b - a) * (1.0f - w);
+  s = fmaxf(s, 1.0f);
+  for (int i = threadIdx.x; i < per; i += blockDim.x) x0[i] = fminf(fmaxf(x0[i], -s), s) / s;
+}
+
 // One block per sample: CFG combine, x0 prediction, optional dynamic threshold (torch.quantile, linear).
 __global__ __launch_bounds__(1024) void cfg_x0_kernel(const float* x, const float* ec, const float* eu, float scale,
                                                       const int64_t* t, const float* ta, const float* tb, int mode,
@@ -1083,41 +1117,99 @@ __global__ __launch_bounds__(1024) void cfg_x0_kernel(const float* x, const floa
     }
     sv[i] = v;
   }
+  cfg_threshold(sv, x0_out + (size_t)n * per, per, npad, p);
+}
+
+// Guided prediction, optional guidance rescale (Lin et al. 2023, arXiv:2305.08891 §3.4), eps and x0 from either
+// prediction type, dynamic threshold; one block per sample, pc / pu rows read in place at their own strides. The v
+// arm is pred_convert_kernel's ops (no division: alpha = 0 is representable). The rescale factor comes from two-pass
+// double sums in a fixed order (thread-strided, wave butterfly, wave partials in index order): no atomics.
+DMC_DEV void guide_block_sum2(double& a, double& b, double* sm) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    a += __shfl_xor(a, o, 64);
+    b += __shfl_xor(b, o, 64);
+  }
+  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    sm[2 * w] = a;
+    sm[2 * w + 1] = b;
+  }
   __syncthreads();
-  if (!(p > 0.f)) {
+  a = 0.0;
+  b = 0.0;
+  for (int k = 0; k < nw; ++k) {
+    a += sm[2 * k];
+    b += sm[2 * k + 1];
+  }
+  __syncthreads();   // sm is reused
+}
+
+__global__ __launch_bounds__(1024) void cfg_guide_kernel(int pred_type, const float* x, const float* pc, long pc_ld,
+                                                         const float* pu, long pu_ld, float scale, float rescale,
+                                                         const int64_t* t, const float* sa, const float* s1, int T,
+                                                         int per, int npad, float p, float* eps_out, float* x0_out) {
+  extern __shared__ double guide_sm[];   // the wave partials of the sums, then |x0| for the sort (>= 256 bytes)
+  float* sv = (float*)guide_sm;
+  const int n = blockIdx.x;
+  const float* xr = x + (size_t)n * per;
+  const float* cr = pc + (size_t)n * pc_ld;
+  const float* ur = pu + (size_t)n * pu_ld;
+  const long tt = clamp_t(t[n], T);
+  const float san = sa[tt], s1n = s1[tt];
+  float f = 1.0f;
+  if (rescale > 0.f) {
+    double sc = 0.0, sg = 0.0;
     for (int i = threadIdx.x; i < per; i += blockDim.x) {
-      const float x0 = x0_out[(size_t)n * per + i];
-      x0_out[(size_t)n * per + i] = fminf(fmaxf(x0, -1.0f), 1.0f);
+      const float c = cr[i], u = ur[i];
+      const float d = c - u;
+      const float g = u + scale * d;
+      sc += (double)c;
+      sg += (double)g;
     }
-    return;
+    guide_block_sum2(sc, sg, guide_sm);
+    const double mc = sc / (double)per, mg = sg / (double)per;
+    double qc = 0.0, qg = 0.0;
+    for (int i = threadIdx.x; i < per; i += blockDim.x) {
+      const float c = cr[i], u = ur[i];
+      const float d = c - u;
+      const float g = u + scale * d;
+      const double dc = (double)c - mc, dg = (double)g - mg;
+      qc += dc * dc;
+      qg += dg * dg;
+    }
+    guide_block_sum2(qc, qg, guide_sm);
+    // a guided row without spread has no deviation to match: it is left as it is (f = 1)
+    if (qg > 0.0) f = (float)((double)rescale * sqrt(qc / qg) + (1.0 - (double)rescale));
   }
-  // bitonic sort of |x0| (padding +inf sorts last)
-  for (int k = 2; k <= npad; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < npad; i += blockDim.x) {
-        const int ixj = i ^ j;
-        if (ixj > i) {
-          const float a = sv[i], b = sv[ixj];
-          const bool up = (i & k) == 0;
-          if ((a > b) == up) { sv[i] = b; sv[ixj] = a; }
-        }
+  for (int i = threadIdx.x; i < npad; i += blockDim.x) {
+    float v = INFINITY;
+    if (i < per) {
+      const float c = cr[i], u = ur[i];
+      const float d = c - u;
+      float g = u + scale * d;
+      if (rescale > 0.f) g = g * f;
+      const float xx = xr[i];
+      float e, x0;
+      if (pred_type == DMC_PRED_V) {
+        const float uu = s1n * xx;
+        const float qq = san * g;
+        e = uu + qq;
+        const float pp = san * xx;
+        const float rr = s1n * g;
+        x0 = pp - rr;
+      } else {
+        e = g;
+        const float num = xx - s1n * g;
+        x0 = num / san;
       }
-      __syncthreads();
+      if (eps_out) eps_out[(size_t)n * per + i] = e;
+      x0_out[(size_t)n * per + i] = x0;
+      v = fabsf(x0);
     }
+    sv[i] = v;
   }
-  // torch.quantile(..., interpolation='linear'): rank = q*(n-1) in fp32, lerp
-  const float rank = p * (float)(per - 1);
-  const float lof = floorf(rank);
-  const int lo = (int)lof;
-  const int hi = (int)ceilf(rank);
-  const float w = rank - lof;
-  const float a = sv[lo], b = sv[hi];
-  float s = (w < 0.5f) ? a + w * (b - a) : b - (b - a) * (1.0f - w);
-  s = fmaxf(s, 1.0f);
-  for (int i = threadIdx.x; i < per; i += blockDim.x) {
-    const float x0 = x0_out[(size_t)n * per + i];
-    x0_out[(size_t)n * per + i] = fminf(fmaxf(x0, -s), s) / s;
-  }
+  cfg_threshold(sv, x0_out + (size_t)n * per, per, npad, p);
 }
 
 // ---------------- multi-tensor ----------------
@@ -1641,6 +1733,26 @@ extern "C" int dmc_cfg_x0(const float* x, const float* ec, const float* eu, floa
   cfg_x0_kernel<<<N, 1024, npad * sizeof(float), dmc::as_stream(stream)>>>(x, ec, eu, scale, t, ta, tb, mode, per, npad,
                                                                           p, eps_out, x0_out);
   return dmc::check_launch("dmc_cfg_x0");
+}
+
+extern "C" int dmc_cfg_guide(int pred_type, const float* x, const float* pc, long pc_stride, const float* pu,
+                             long pu_stride, float scale, float rescale, const int64_t* t, const float* sa,
+                             const float* s1, int T, int N, int per, float p, float* eps_out, float* x0_out,
+                             void* stream) {
+  DMC_REQUIRE(pred_type == DMC_PRED_EPS || pred_type == DMC_PRED_V, "cfg_guide: unknown prediction type %d", pred_type);
+  DMC_REQUIRE(T > 0 && N > 0 && per > 0, "cfg_guide: T %d, N %d, per_sample %d must be positive", T, N, per);
+  DMC_REQUIRE(x && pc && pu && t && sa && s1 && x0_out, "cfg_guide: only eps_out may be NULL");
+  DMC_REQUIRE(pc_stride >= per && pu_stride >= per, "cfg_guide: row strides %ld, %ld are below per_sample %d", pc_stride,
+              pu_stride, per);
+  DMC_REQUIRE(rescale >= 0.f && rescale <= 1.f, "cfg_guide: rescale %g is not in [0, 1]", (double)rescale);
+  DMC_REQUIRE(!(p >= 1.f), "cfg_guide: p_threshold %g is not below 1", (double)p);
+  int npad = 1;
+  while (npad < per) npad <<= 1;
+  DMC_REQUIRE(npad <= 16384, "cfg_guide: %d elements per sample exceeds 16384", per);
+  const size_t lds = npad * sizeof(float) < 256 ? 256 : npad * sizeof(float);   // 16 waves x 2 double partials
+  cfg_guide_kernel<<<N, 1024, lds, dmc::as_stream(stream)>>>(pred_type, x, pc, pc_stride, pu, pu_stride, scale, rescale,
+                                                             t, sa, s1, T, per, npad, p, eps_out, x0_out);
+  return dmc::check_launch("dmc_cfg_guide");
 }
 
 extern "C" int dmc_ema_update(const dmc_tensor_ref* refs, int count, float decay, void* stream) {

@@ -51,6 +51,13 @@ class EditMixin:
     def _edit_image(st):
         return st
 
+    def _refuse_zero_terminal(self, what):
+        """The blend table (_edit.blend_coefficients) needs 0 < alphas_cumprod along the walk, and an image noised to
+        T-1 of a zero terminal SNR schedule is pure noise: nothing of it is left to edit."""
+        if getattr(self, "rescale_zero_snr", False):
+            raise ValueError(f"{what} is not defined on a zero terminal SNR schedule (rescale_zero_snr=True): "
+                             "alphas_cumprod[T-1] is 0")
+
     def _edit_input(self, image):
         if image.dim() != 4:
             raise ValueError(f"image must be [B, C, H, W], got {tuple(image.shape)}")
@@ -95,6 +102,7 @@ class EditMixin:
         _edit.start_index(S, strength) of the sampler's list, then steps i0 .. S-1 of sample (cfg_scale None) or
         sample_with_cfg. noise: callable (j, which) -> tensor, which = 'start' (j = 0) or 'step' (the j-th executed
         step's z, for a sampler that draws one); None draws torch.randn_like."""
+        self._refuse_zero_terminal("img2img")
         cfg = _check_cfg(y, cfg_scale, p_threshold)
         image = self._edit_input(image)
         dev, B = image.device, image.shape[0]
@@ -145,6 +153,7 @@ class EditMixin:
         with row 2i + renoise of _edit.blend_coefficients. noise: callable (j, which) -> tensor for walk entry j,
         which = 'start' (j = 0, without x_T), 'step', 'known', 'renoise', asked for in that order and only where the
         entry reads the draw; None draws torch.randn_like."""
+        self._refuse_zero_terminal("inpaint")
         cfg = _check_cfg(y, cfg_scale, p_threshold)
         image = self._edit_input(image)
         dev, B = image.device, image.shape[0]

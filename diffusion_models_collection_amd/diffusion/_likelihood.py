@@ -45,6 +45,9 @@ class LikelihoodMixin:
         that makes x_t. y gives the conditional bound (there is no guided variant: a guided score is no likelihood).
         Returns fp32 device tensors: vb, xstart_mse, eps_mse [B, S] (columns in the order walked), timesteps [S]
         (int64), prior_bpd [B], and total_bpd [B] = vb.sum(1) + prior_bpd when all T steps were walked, else None."""
+        if getattr(self, "rescale_zero_snr", False):
+            raise ValueError("calc_bpd is not defined on a zero terminal SNR schedule (rescale_zero_snr=True): the "
+                             "bound's tables need 0 < alphas_cumprod")
         learned = variance == "learned"
         lr = getattr(self, "variance_type", "fixed") == "learned_range"
         if learned and not lr:

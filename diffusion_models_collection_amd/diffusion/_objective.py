@@ -41,11 +41,19 @@ def check_gamma(gamma):
     return g
 
 
-def min_snr_weights(alphas_cumprod, gamma, prediction_type):
-    """float32 [T]: the min-SNR-gamma weight of every timestep for the given prediction type."""
+def min_snr_weights(alphas_cumprod, gamma, prediction_type, zero_terminal=False):
+    """float32 [T]: the min-SNR-gamma weight of every timestep for the given prediction type. zero_terminal=True admits
+    the table of a zero-terminal-SNR schedule (arXiv:2305.08891), exactly one trailing alphas_cumprod = 0, for 'v' only:
+    its closed form min(a, gamma * (1 - a)) is 0 there, where the eps form divides by a."""
     g = check_gamma(gamma)
     check_prediction_type(prediction_type)
     a = np.asarray(alphas_cumprod, np.float32).astype(np.float64)
+    if zero_terminal:
+        if prediction_type != "v" or a.ndim != 1 or a.size < 2 or a[-1] != 0:
+            raise ValueError("min_snr_weights: zero_terminal=True needs prediction_type='v' and a [T >= 2] table whose "
+                             "last entry, and no other, is 0 (a zero terminal SNR schedule)")
+        w = min_snr_weights(a[:-1], g, prediction_type)
+        return np.concatenate([w, np.zeros(1, np.float32)])
     if a.ndim != 1 or bool(((a <= 0) | (a >= 1)).any()):
         raise ValueError("min_snr_weights: alphas_cumprod must be a [T] table strictly between 0 and 1 in fp32 (the "
                          "SNR is undefined otherwise)")

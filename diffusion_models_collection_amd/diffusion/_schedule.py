@@ -132,15 +132,50 @@ def make_betas(num_timesteps, beta_start, beta_end, beta_schedule, prims=IEEE):
     raise ValueError(f"Unknown beta schedule: {beta_schedule}")
 
 
-def build_tables(num_timesteps, beta_start, beta_end, beta_schedule, prims=IEEE):
-    """Every DDPM table (diffusion/ddpm.py:38-71) in the reference's op order; fp32 numpy arrays."""
+def rescale_zero_terminal_snr(alphas_cumprod):
+    """Algorithm 1 of Lin et al. 2023 (arXiv:2305.08891): shift and scale sqrt(alphas_cumprod) so that its last entry
+    is 0 and its first is kept. float64 from the fp32 table, each entry rounded to fp32 once (the rule of _dpm.py):
+        s = sqrt(ac);  s' = (s - s[T-1]) * (s[0] / (s[0] - s[T-1]));  ac' = s'^2
+    The last entry is exactly 0; a table that was strictly decreasing must stay so in fp32 (ValueError otherwise)."""
+    a = np.asarray(alphas_cumprod, _F).astype(np.float64)
+    if a.ndim != 1 or a.size < 2 or bool(((a <= 0) | (a > 1)).any()) or bool((np.diff(a) >= 0).any()):
+        raise ValueError("zero terminal SNR: alphas_cumprod must be a strictly decreasing [T >= 2] table in (0, 1]")
+    s = np.sqrt(a)
+    s = (s - s[-1]) * (s[0] / (s[0] - s[-1]))
+    out = (s * s).astype(_F)
+    if bool((np.diff(out) >= 0).any()) or out[-1] != 0:
+        raise ValueError("zero terminal SNR: the rescaled alphas_cumprod is not strictly decreasing in fp32")
+    return out
+
+
+def build_tables(num_timesteps, beta_start, beta_end, beta_schedule, prims=IEEE, zero_terminal_snr=False):
+    """Every DDPM table (diffusion/ddpm.py:38-71) in the reference's op order; fp32 numpy arrays.
+
+    zero_terminal_snr=True (not in the reference): alphas_cumprod is rescale_zero_terminal_snr of the schedule's own,
+    alphas[t] = ac[t] / ac[t-1] (ac[-1] = 1), betas = 1 - alphas, and every other table follows by the formulas below.
+    Then alphas_cumprod[T-1] = alphas[T-1] = 0 and betas[T-1] = 1, so sqrt_recip_alphas, sqrt_recip_alphas_cumprod and
+    sqrt_recipm1_alphas_cumprod are +inf at T-1 and nowhere else; every other entry is finite, with
+    posterior_mean_coef2[T-1] = 0 and posterior_mean_coef1[T-1] = sqrt(alphas_cumprod[T-2]). Only a v-prediction
+    sampler that never divides by alpha can use such tables (ddpm.py ObjectiveMixin)."""
     one = _F(1)
     b = make_betas(num_timesteps, beta_start, beta_end, beta_schedule, prims)
     al = (one - b).astype(_F)
     ac = cumprod_f32(al)
     acp = np.concatenate([np.array([1.0], _F), ac[:-1]]).astype(_F)
+    if zero_terminal_snr:
+        ac = rescale_zero_terminal_snr(ac)
+        acp = np.concatenate([np.array([1.0], _F), ac[:-1]]).astype(_F)
+        al = (ac / acp).astype(_F)
+        b = (one - al).astype(_F)
+    with np.errstate(divide="ignore"):                   # 1 / 0 = +inf at T-1 of a zero-terminal-SNR table only
+        tabs = _tables_from(b, al, ac, acp, prims)
+    return {k: np.ascontiguousarray(v, _F) for k, v in tabs.items()}
+
+
+def _tables_from(b, al, ac, acp, prims):
+    one = _F(1)
     pv = (b * (one - acp) / (one - ac)).astype(_F)
-    tabs = {
+    return {
         "betas": b,
         "alphas": al,
         "alphas_cumprod": ac,
@@ -156,9 +191,17 @@ def build_tables(num_timesteps, beta_start, beta_end, beta_schedule, prims=IEEE)
         # recomputed by the reference on every p_mean_variance call (ddpm.py:170-171)
         "sqrt_recip_alphas_cumprod": prims.sqrt(one / ac),
     }
-    return {k: np.ascontiguousarray(v, _F) for k, v in tabs.items()}
 
 
 def ddim_timesteps(num_timesteps, num_inference_steps):
     """linspace(T-1, 0, S).round().long() (diffusion/ddim.py:71-85); round half to even like torch.round."""
     return np.rint(linspace_f32(num_timesteps - 1, 0, num_inference_steps)).astype(np.int64)
+
+
+def trailing_timesteps(num_timesteps, num_inference_steps):
+    """'trailing' spacing of arXiv:2305.08891 (table 2): round(arange(T, 0, -T/S)) - 1, numpy's round half to even.
+    It starts at T-1 like the linspace grid and ends at about T/S - 1 instead of 0: every step is T/S long."""
+    T, S = int(num_timesteps), int(num_inference_steps)
+    if not 1 <= S <= T:
+        raise ValueError(f"trailing timesteps: num_inference_steps must be in [1, {T}], got {num_inference_steps}")
+    return (np.round(np.arange(T, 0, -T / S)[:S]) - 1).astype(np.int64)

@@ -14,6 +14,9 @@ prediction_type='v' (not in the reference; ddpm.py ObjectiveMixin): one dmc_pred
 hands eps and x0 to the same step kernel.
 img2img / inpaint (not in the reference; _edit_loop.EditMixin) run the same steps from, or around, a given image;
 invert runs the eta = 0 step with (t, t_next) swapped, from an image up to its latent.
+rescale_zero_snr / timestep_spacing='trailing' / sample_with_cfg(guidance_rescale=...) (not in the reference;
+arXiv:2305.08891): the schedule rescaled to zero terminal SNR, the paper's inference grid, and the rescaled guidance of
+dmc_cfg_guide (ddpm.py ObjectiveMixin._cfg_guide).
 calc_bpd (not in the reference; _likelihood.LikelihoodMixin) is the variational bound over all T timesteps, whatever
 the number of inference steps.
 """
@@ -33,15 +36,25 @@ from .ddpm import ObjectiveMixin, _require_cuda, diffusion_loss, make_betas
 class DDIM(ObjectiveMixin, EditMixin, LikelihoodMixin):
     """DDIM diffusion process with accelerated sampling (diffusion/ddim.py:13-351)."""
 
+    SPACINGS = ("linspace", "trailing")
+
     def __init__(self, num_timesteps=1000, num_inference_steps=50, beta_start=0.0001, beta_end=0.02,
-                 beta_schedule='linear', eta=0.0, device='cuda', prediction_type='eps', variance_type='fixed'):
-        self.prediction_type = _objective.check_prediction_type(prediction_type)
-        self.variance_type = _vlb.check_variance_type(variance_type)
+                 beta_schedule='linear', eta=0.0, device='cuda', prediction_type='eps', variance_type='fixed',
+                 rescale_zero_snr=False, timestep_spacing='linspace'):
+        """Not in the reference: rescale_zero_snr=True rescales the schedule to zero terminal SNR (arXiv:2305.08891;
+        _schedule.build_tables; 'v' and 'fixed' only), timestep_spacing='trailing' is that paper's inference grid
+        (_schedule.trailing_timesteps); 'linspace' is the reference's."""
+        if timestep_spacing not in self.SPACINGS:
+            raise ValueError(f"Unknown timestep spacing: {timestep_spacing} (expected one of {self.SPACINGS})")
+        self.timestep_spacing = timestep_spacing
+        self.rescale_zero_snr = bool(rescale_zero_snr)
+        self._set_types(prediction_type, variance_type)
         self.num_timesteps = num_timesteps
         self.num_inference_steps = num_inference_steps
         self.eta = eta
         self.device = device
-        tabs = _schedule.build_tables(num_timesteps, beta_start, beta_end, beta_schedule)
+        tabs = _schedule.build_tables(num_timesteps, beta_start, beta_end, beta_schedule,
+                                      zero_terminal_snr=self.rescale_zero_snr)
         for k in ("betas", "alphas", "alphas_cumprod", "sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod"):
             setattr(self, k, torch.from_numpy(tabs[k]).to(device))
         self._setup_inference_timesteps()
@@ -50,7 +63,10 @@ class DDIM(ObjectiveMixin, EditMixin, LikelihoodMixin):
         return make_betas(timesteps, 0, 0, "cosine").to(device)
 
     def _setup_inference_timesteps(self):
-        ts = _schedule.ddim_timesteps(self.num_timesteps, self.num_inference_steps)
+        if self.timestep_spacing == "trailing":
+            ts = _schedule.trailing_timesteps(self.num_timesteps, self.num_inference_steps)
+        else:
+            ts = _schedule.ddim_timesteps(self.num_timesteps, self.num_inference_steps)
         self.inference_timesteps = torch.from_numpy(ts).to(self.device)
 
     def _tab(self, name, dev):
@@ -130,11 +146,14 @@ class DDIM(ObjectiveMixin, EditMixin, LikelihoodMixin):
             eps, x0 = self._convert(eps, x, t)
         return self.p_sample(model, x, t, tn, y, clip_denoised=clip, eps=eps, x0_pred=x0, noise=z)
 
-    def _step_cfg(self, model, x, t, tn, y, z, cfg_scale, p_threshold):
+    def _step_cfg(self, model, x, t, tn, y, z, cfg_scale, p_threshold, guidance_rescale=0.0):
         """One step of sample_with_cfg(): shared with img2img / inpaint."""
-        eps_c, eps_u = self._cfg_pair(model, x, t, y)
-        eps_g, x0 = K.cfg_x0(x.contiguous(), eps_c.contiguous(), eps_u.contiguous(), cfg_scale, t,
-                             self._tab("alphas_cumprod", x.device), None, 0, p_threshold)
+        if self._use_guide(guidance_rescale):
+            eps_g, x0, _ = self._cfg_guide(model, x, t, y, cfg_scale, guidance_rescale, p_threshold)
+        else:
+            eps_c, eps_u = self._cfg_pair(model, x, t, y)
+            eps_g, x0 = K.cfg_x0(x.contiguous(), eps_c.contiguous(), eps_u.contiguous(), cfg_scale, t,
+                                 self._tab("alphas_cumprod", x.device), None, 0, p_threshold)
         return self.p_sample(model, x, t, tn, y=None, clip_denoised=False, eps=eps_g, x0_pred=x0, noise=z)
 
     def _edit_steps(self):
@@ -230,12 +249,14 @@ class DDIM(ObjectiveMixin, EditMixin, LikelihoodMixin):
 
     @torch.no_grad()
     def sample_with_cfg(self, model, shape, y, cfg_scale=3.0, p_threshold=0.995, return_all_timesteps=False,
-                        x_T=None, noise=None):
-        """DDIM + classifier-free guidance + dynamic thresholding (diffusion/ddim.py:251-346)."""
+                        x_T=None, noise=None, guidance_rescale=0.0):
+        """DDIM + classifier-free guidance + dynamic thresholding (diffusion/ddim.py:251-346). guidance_rescale (not in
+        the reference): as DDPM.sample_with_cfg."""
         if y is None:
             raise ValueError("CFG sampling requires class labels y.")
         if p_threshold is not None and not (0.0 < float(p_threshold) < 1.0):
             raise ValueError("p_threshold must be in (0, 1) or None")
+        rescale = self._guidance_rescale(guidance_rescale)
         batch_size = shape[0]
         device = self.device
         img = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float()
@@ -254,7 +275,7 @@ class DDIM(ObjectiveMixin, EditMixin, LikelihoodMixin):
             return (x, tab[i], tab[i + 1], y) + ((z,) if z is not None else ())
 
         def fn(x, t, tn, yy, z=None):
-            return self._step_cfg(model, x, t, tn, yy, z, cfg_scale, p_threshold)
+            return self._step_cfg(model, x, t, tn, yy, z, cfg_scale, p_threshold, rescale)
 
         def record(i, x):
             bar.update(1)
@@ -262,7 +283,8 @@ class DDIM(ObjectiveMixin, EditMixin, LikelihoodMixin):
                 imgs.append(x.cpu())
 
         cache = None if return_all_timesteps else cache_for(
-            model, ("ddim_cfg", self.prediction_type, self.variance_type, self.eta, has_z, float(cfg_scale), p_threshold, ac.data_ptr()),
+            model, ("ddim_cfg", self.prediction_type, self.variance_type, self.eta, has_z, float(cfg_scale), p_threshold, rescale,
+                    ac.data_ptr()),
             self, img)
         img = run_loop(img, S, inputs, fn, StepGraph.eligible(model, img, True, False),
                        record, cache=cache, const=(3,))

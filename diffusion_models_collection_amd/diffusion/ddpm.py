@@ -33,6 +33,12 @@ sampler's importance weight and feeds its loss history:
   any loss            -> dmc_objective_is / dmc_hybrid_objective_is (the same kernels with iw[t] and the per-sample loss), via
                          _ObjectiveISFn / _HybridISFn, then dmc_ts_history_update
 Without a sampler nothing new is launched.
+DDPM(rescale_zero_snr=True) (not in the reference; arXiv:2305.08891) rescales the schedule to zero terminal SNR
+(_schedule.build_tables; 'v' and 'fixed' only: ObjectiveMixin._set_types), and sample_with_cfg(guidance_rescale=...)
+rescales the guided prediction:
+  CFG on such a schedule, or rescaled -> dmc_cfg_guide (guidance, rescale, eps and x0 from the model's own 2B-row output,
+                                         threshold: one launch where dmc_pred_convert + dmc_cfg_x0 stand)
+With the defaults nothing new is launched.
 """
 import numpy as np
 import torch
@@ -176,16 +182,36 @@ class ObjectiveMixin:
 
     prediction_type = "eps"
     variance_type = "fixed"
+    rescale_zero_snr = False
+
+    def _set_types(self, prediction_type, variance_type):
+        """Both types, checked together: a zero-terminal-SNR schedule (alphas_cumprod[T-1] = 0) has no eps form at
+        T-1 and no learned-variance table (_vlb.learned_coefficients needs 0 < alphas_cumprod)."""
+        prediction_type = _objective.check_prediction_type(prediction_type)
+        variance_type = _vlb.check_variance_type(variance_type)
+        if self.rescale_zero_snr and (prediction_type != "v" or variance_type != "fixed"):
+            raise ValueError("a zero terminal SNR schedule (rescale_zero_snr=True) needs prediction_type='v' and "
+                             f"variance_type='fixed', got {prediction_type!r} and {variance_type!r}: eps is not "
+                             "defined where alphas_cumprod is 0")
+        self.prediction_type, self.variance_type = prediction_type, variance_type
+
+    @staticmethod
+    def _guidance_rescale(guidance_rescale):
+        """guidance_rescale as a float; ValueError unless it is a number in [0, 1] (arXiv:2305.08891 uses 0.7)."""
+        g = guidance_rescale
+        if isinstance(g, (bool, str, bytes)) or not isinstance(g, (int, float)) or not 0.0 <= float(g) <= 1.0:
+            raise ValueError(f"guidance_rescale must be a number in [0, 1], got {guidance_rescale!r}")
+        return float(g)
 
     def set_prediction_type(self, prediction_type):
         """'eps' or 'v'. Drops the sampler's cached step graphs (their steps were captured for the old type)."""
-        self.prediction_type = _objective.check_prediction_type(prediction_type)
+        self._set_types(prediction_type, self.variance_type)
         self.__dict__.pop("_step_graphs", None)
 
     def set_variance_type(self, variance_type):
         """'fixed', or 'learned_range': the model returns 2C channels, the prediction and the variance interpolation v
         (arXiv:2102.09672 §3.1). Drops the sampler's cached step graphs, as set_prediction_type does."""
-        self.variance_type = _vlb.check_variance_type(variance_type)
+        self._set_types(self.prediction_type, variance_type)
         self.__dict__.pop("_step_graphs", None)
 
     def _lvar_table(self, dev):
@@ -275,7 +301,8 @@ class ObjectiveMixin:
         cache = self.__dict__.setdefault("_snr_tables", {})
         w = cache.get(key)
         if w is None or w.device != dev:
-            w = torch.from_numpy(_objective.min_snr_weights(self.alphas_cumprod.cpu().numpy(), *key)).to(dev)
+            w = torch.from_numpy(_objective.min_snr_weights(self.alphas_cumprod.cpu().numpy(), *key,
+                                                            zero_terminal=self.rescale_zero_snr)).to(dev)
             cache[key] = w
         return w
 
@@ -317,17 +344,38 @@ class ObjectiveMixin:
             eps, _ = self._convert(eps, img, t, want_x0=False)
         return eps[:B], eps[B:], both
 
+    def _use_guide(self, guidance_rescale):
+        """dmc_cfg_guide stands in for the dmc_pred_convert + dmc_cfg_x0 path when the guidance is rescaled or the
+        schedule reaches alphas_cumprod = 0 (which that path cannot represent); otherwise the step is unchanged."""
+        return guidance_rescale > 0 or self.rescale_zero_snr
+
+    def _cfg_guide(self, model, img, t, y, cfg_scale, guidance_rescale, p_threshold, want_eps=True):
+        """(guided eps or None, guided and thresholded x0, the batched model output): ONE 2B forward, then ONE
+        dmc_cfg_guide launch that reads the conditional and unconditional rows (for learned_range their prediction
+        channels) in place."""
+        B, C = img.shape[0], img.shape[1]
+        both = model(torch.cat([img, img], 0), torch.cat([t, t], 0), torch.cat([y, torch.zeros_like(y)], 0))
+        _require_cuda(img, both)
+        both = both.contiguous().float()
+        pred = self._check_out(both, img)[:, :C] if self.variance_type == "learned_range" else both
+        dev = img.device
+        eps, x0 = K.cfg_guide(self.prediction_type, img.contiguous().float(), pred[:B], pred[B:], cfg_scale,
+                              guidance_rescale, t.to(dev).long().contiguous(), self._tab("sqrt_alphas_cumprod", dev),
+                              self._tab("sqrt_one_minus_alphas_cumprod", dev), p_threshold, want_eps=want_eps)
+        return eps, x0, both
+
 
 class DDPM(ObjectiveMixin, EditMixin, LikelihoodMixin):
     """DDPM diffusion process (diffusion/ddpm.py:15-332)."""
 
     def __init__(self, num_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule='linear', device='cuda',
-                 prediction_type='eps', variance_type='fixed'):
-        self.prediction_type = _objective.check_prediction_type(prediction_type)
-        self.variance_type = _vlb.check_variance_type(variance_type)
+                 prediction_type='eps', variance_type='fixed', rescale_zero_snr=False):
+        self.rescale_zero_snr = bool(rescale_zero_snr)
+        self._set_types(prediction_type, variance_type)
         self.num_timesteps = num_timesteps
         self.device = device
-        tabs = _schedule.build_tables(num_timesteps, beta_start, beta_end, beta_schedule)
+        tabs = _schedule.build_tables(num_timesteps, beta_start, beta_end, beta_schedule,
+                                      zero_terminal_snr=self.rescale_zero_snr)
         for k, v in tabs.items():
             setattr(self, k, torch.from_numpy(v).to(device))
 
@@ -455,13 +503,16 @@ class DDPM(ObjectiveMixin, EditMixin, LikelihoodMixin):
         """One step of sample(): shared with img2img / inpaint."""
         return self.p_sample(model, x, t, y, noise=z)
 
-    def _step_cfg(self, model, x, t, y, z, cfg_scale, p_threshold):
+    def _step_cfg(self, model, x, t, y, z, cfg_scale, p_threshold, guidance_rescale=0.0):
         """One step of sample_with_cfg(): shared with img2img / inpaint."""
         dev = x.device
-        eps_c, eps_u, both = self._cfg_pair_out(model, x, t, y)
-        eps_g, x0 = K.cfg_x0(x.contiguous(), eps_c.contiguous(), eps_u.contiguous(), cfg_scale, t,
-                             self._tab("sqrt_recip_alphas_cumprod", dev),
-                             self._tab("sqrt_recipm1_alphas_cumprod", dev), 1, p_threshold)
+        if self._use_guide(guidance_rescale):
+            eps_g, x0, both = self._cfg_guide(model, x, t, y, cfg_scale, guidance_rescale, p_threshold)
+        else:
+            eps_c, eps_u, both = self._cfg_pair_out(model, x, t, y)
+            eps_g, x0 = K.cfg_x0(x.contiguous(), eps_c.contiguous(), eps_u.contiguous(), cfg_scale, t,
+                                 self._tab("sqrt_recip_alphas_cumprod", dev),
+                                 self._tab("sqrt_recipm1_alphas_cumprod", dev), 1, p_threshold)
         # learned_range: the variance is the conditional half's (DiT's convention), the output's first B rows
         cond = both[:x.shape[0]] if self.variance_type == "learned_range" else None
         return self.p_sample(model, x, t, y=None, clip_denoised=False, eps=eps_g, x0_pred=x0, noise=z, model_out=cond)
@@ -523,12 +574,16 @@ class DDPM(ObjectiveMixin, EditMixin, LikelihoodMixin):
 
     @torch.no_grad()
     def sample_with_cfg(self, model, shape, y, cfg_scale=3.0, p_threshold=0.995, return_all_timesteps=False,
-                        x_T=None, noise=None):
-        """Classifier-free guidance + dynamic thresholding (diffusion/ddpm.py:254-332); x_T / noise as sample()."""
+                        x_T=None, noise=None, guidance_rescale=0.0):
+        """Classifier-free guidance + dynamic thresholding (diffusion/ddpm.py:254-332); x_T / noise as sample().
+        guidance_rescale (not in the reference; arXiv:2305.08891 §3.4, in [0, 1], the paper uses 0.7) pulls the guided
+        prediction's per-sample standard deviation towards the conditional one's; above 0, or on a zero-terminal-SNR
+        schedule, the step's guidance is ONE dmc_cfg_guide launch on the model's own output."""
         if y is None:
             raise ValueError("CFG sampling requires class labels y.")
         if p_threshold is not None and not (0.0 < float(p_threshold) < 1.0):
             raise ValueError("p_threshold must be in (0, 1) or None")
+        rescale = self._guidance_rescale(guidance_rescale)
         batch_size = shape[0]
         device = self.device
         img = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float()
@@ -543,7 +598,7 @@ class DDPM(ObjectiveMixin, EditMixin, LikelihoodMixin):
             return x, ts[T - 1 - i], self._noise(noise, i, x)
 
         def fn(x, t, z):
-            return self._step_cfg(model, x, t, y, z, cfg_scale, p_threshold)
+            return self._step_cfg(model, x, t, y, z, cfg_scale, p_threshold, rescale)
 
         def record(i, x):
             bar.update(1)

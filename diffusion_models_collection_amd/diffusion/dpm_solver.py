@@ -11,7 +11,9 @@ the step function's first input and its output, so the history rides through gra
 and a cached graph that replays from step 0 starts from the caller's fresh state. Row 0 has c1 = 0 and never reads
 the history, so the same captured step serves every i. CFG reuses dmc_cfg_x0 (guided eps, x0, dynamic threshold)
 unchanged and hands its x0 to dmc_dpm_step. With prediction_type='v' (ddpm.py ObjectiveMixin) dmc_pred_convert turns
-the model output into that x0 (plain path) or into the two eps halves (CFG) first.
+the model output into that x0 (plain path) or into the two eps halves (CFG) first. sample_with_cfg(guidance_rescale > 0)
+takes its x0 from dmc_cfg_guide instead (arXiv:2305.08891 §3.4). A zero-terminal-SNR schedule is refused: the solver
+steps in half-log-SNR, which is -inf there.
 """
 import torch
 from tqdm import tqdm
@@ -26,18 +28,23 @@ from .ddpm import _require_cuda
 class DPMSolver(DDIM):
     """DPM-Solver++ with DDIM's tables, q_sample / p_losses / _extract and sampling entry points."""
 
+    SPACINGS = _dpm.SPACINGS
+
     def __init__(self, num_timesteps=1000, num_inference_steps=20, beta_start=0.0001, beta_end=0.02,
                  beta_schedule='linear', solver_order=2, timestep_spacing='logsnr', lower_order_final=True,
-                 device='cuda', prediction_type='eps', variance_type='fixed'):
+                 device='cuda', prediction_type='eps', variance_type='fixed', rescale_zero_snr=False):
+        if rescale_zero_snr:
+            raise ValueError("DPMSolver has no zero terminal SNR schedule (rescale_zero_snr=True): the solver steps in "
+                             "half-log-SNR, which is -inf where alphas_cumprod is 0; use DDIM or DDPM")
         if solver_order not in (1, 2):
             raise ValueError(f"solver_order must be 1 or 2, got {solver_order}")
         if timestep_spacing not in _dpm.SPACINGS:
             raise ValueError(f"Unknown timestep spacing: {timestep_spacing} (expected one of {_dpm.SPACINGS})")
         self.solver_order = solver_order
-        self.timestep_spacing = timestep_spacing
         self.lower_order_final = bool(lower_order_final)
         super().__init__(num_timesteps, num_inference_steps, beta_start, beta_end, beta_schedule, eta=0.0,
-                         device=device, prediction_type=prediction_type, variance_type=variance_type)
+                         device=device, prediction_type=prediction_type, variance_type=variance_type,
+                         timestep_spacing=timestep_spacing)
 
     def _setup_inference_timesteps(self):
         """num_inference_steps keeps the request; with 'logsnr' len(inference_timesteps) can be below it."""
@@ -100,12 +107,15 @@ class DPMSolver(DDIM):
             K.dpm_step(x, eps.contiguous().float(), k, coef, clip=clip, x0_prev=st[1], out=new[0], x0_out=new[1])
         return new
 
-    def _step_cfg(self, model, st, t, k, y, coef, cfg_scale, p_threshold):
+    def _step_cfg(self, model, st, t, k, y, coef, cfg_scale, p_threshold, guidance_rescale=0.0):
         """One step of sample_with_cfg(): shared with img2img / inpaint."""
         x = st[0]
-        eps_c, eps_u = self._cfg_pair(model, x, t, y)
-        _, x0 = K.cfg_x0(x, eps_c.contiguous(), eps_u.contiguous(), cfg_scale, t,
-                         self._tab("alphas_cumprod", x.device), None, 0, p_threshold)
+        if self._use_guide(guidance_rescale):
+            _, x0, _ = self._cfg_guide(model, x, t, y, cfg_scale, guidance_rescale, p_threshold, want_eps=False)
+        else:
+            eps_c, eps_u = self._cfg_pair(model, x, t, y)
+            _, x0 = K.cfg_x0(x, eps_c.contiguous(), eps_u.contiguous(), cfg_scale, t,
+                             self._tab("alphas_cumprod", x.device), None, 0, p_threshold)
         new = torch.empty_like(st)
         K.dpm_step(x, None, k, coef, clip=False, x0=x0, x0_prev=st[1], out=new[0], x0_out=new[1])
         return new
@@ -182,13 +192,14 @@ class DPMSolver(DDIM):
 
     @torch.no_grad()
     def sample_with_cfg(self, model, shape, y, cfg_scale=3.0, p_threshold=0.995, return_all_timesteps=False,
-                        x_T=None):
-        """Classifier-free guidance + dynamic thresholding as DDIM.sample_with_cfg: one 2B forward, dmc_cfg_x0 for the
-        guided, thresholded x0, then the solver update from that x0."""
+                        x_T=None, guidance_rescale=0.0):
+        """Classifier-free guidance + dynamic thresholding as DDIM.sample_with_cfg: one 2B forward, dmc_cfg_x0 (with
+        guidance_rescale > 0: dmc_cfg_guide) for the guided, thresholded x0, then the solver update from that x0."""
         if y is None:
             raise ValueError("CFG sampling requires class labels y.")
         if p_threshold is not None and not (0.0 < float(p_threshold) < 1.0):
             raise ValueError("p_threshold must be in (0, 1) or None")
+        rescale = self._guidance_rescale(guidance_rescale)
         batch_size = shape[0]
         img = torch.randn(shape, device=self.device) if x_T is None else x_T.to(self.device).float()
         _require_cuda(img)
@@ -203,8 +214,8 @@ class DPMSolver(DDIM):
             return (st, tab[i], idx[i], y)
 
         def fn(st, t, k, yy):
-            return self._step_cfg(model, st, t, k, yy, coef, cfg_scale, p_threshold)
+            return self._step_cfg(model, st, t, k, yy, coef, cfg_scale, p_threshold, rescale)
 
-        key = self._key("dpm_cfg", coef, float(cfg_scale), p_threshold, ac.data_ptr())
+        key = self._key("dpm_cfg", coef, float(cfg_scale), p_threshold, rescale, ac.data_ptr())
         return self._run(model, self._state(img), S, inputs, fn, return_all_timesteps, key, (3,),
                          f"DPM-Solver++ sampling with CFG scale {cfg_scale}")

@@ -1070,6 +1070,53 @@ def cfg_x0(x, ec, eu, scale, t, ta, tb, mode, p_threshold, out=None):
     return eps, x0
 
 
+def _row_stride(what, rows, ref):
+    """Row stride, in floats, of rows: ref's shape on ref's device, fp32, every sample's elements contiguous and the
+    samples a fixed, non-overlapping pitch apart (a contiguous tensor, or a view of some rows and the leading channels
+    of a larger one, read in place)."""
+    if rows is None or rows.shape != ref.shape or rows.device != ref.device or rows.dtype != torch.float32:
+        got = "None" if rows is None else f"{rows.dtype} {tuple(rows.shape)} on {rows.device}"
+        raise L.DMCError(f"{what}: a prediction is {got}, expected fp32 {tuple(ref.shape)} on {ref.device}")
+    per = ref.numel() // ref.shape[0]
+    ld = rows.stride(0) if rows.shape[0] > 1 else per
+    if not rows[0].is_contiguous() or ld < per:
+        raise L.DMCError(f"{what}: a prediction's samples must each be contiguous and at least {per} floats apart, got "
+                         f"strides {rows.stride()}")
+    return ld
+
+
+def cfg_guide(pred_type, x, pc, pu, scale, rescale, t, sa, s1, p_threshold, want_eps=True, out=None):
+    """(eps or None, x0) of the guided step from the model's own output (dmc_cfg_guide): guidance, the guidance rescale
+    of arXiv:2305.08891 (rescale in [0, 1], 0: none), the conversion of either prediction type and the dynamic
+    threshold. pc / pu: the conditional / unconditional predictions, x's shape, contiguous or row-strided views (the
+    halves of the 2B-row model output, or of a learned_range output's prediction channels) read in place. out: the
+    (eps, x0) buffers to fill; eps None or want_eps=False skips eps."""
+    what = "dmc_cfg_guide"
+    code = _pred_code(what, pred_type)
+    if not x.is_cuda or x.dim() < 1 or x.numel() < 1:
+        raise L.DMCError(f"{what}: x must be a non-empty device tensor, got {tuple(x.shape)} on {x.device}")
+    N = x.shape[0]
+    ldc, ldu = _row_stride(what, pc, x), _row_stride(what, pu, x)
+    if out is not None:
+        eps, x0 = out
+    else:
+        eps, x0 = (torch.empty_like(x) if want_eps else None), torch.empty_like(x)
+    if x0 is None:
+        raise L.DMCError(f"{what}: the x0 buffer is not optional")
+    _same(x, eps, x0, what=what)
+    _fp32_contig(what, x, eps, x0)
+    _steps(N, x.device, t, what=what)
+    T = _tables(what, x.device, sa, s1)
+    if t is None or T is None or sa is None or s1 is None:
+        raise L.DMCError(f"{what}: needs timesteps and the sqrt_alphas_cumprod / sqrt_one_minus_alphas_cumprod tables")
+    if not 0.0 <= float(rescale) <= 1.0:
+        raise L.DMCError(f"{what}: rescale {rescale!r} is not in [0, 1]")
+    p = float(p_threshold) if p_threshold is not None else -1.0
+    check(LIB.dmc_cfg_guide(code, ptr(x), ptr(pc), ldc, ptr(pu), ldu, float(scale), float(rescale), ptr(t), ptr(sa),
+                            ptr(s1), T, N, x.numel() // N, p, ptr(eps), ptr(x0), L.stream()), what)
+    return eps, x0
+
+
 class TensorRefs:
     """Device array of dmc_tensor_ref {a, b, n} for the multi-tensor kernels (uploaded once per pointer set)."""
 

@@ -575,6 +575,25 @@ int dmc_known_blend(const float* x, const float* x0, const float* mask, int mask
 int dmc_cfg_x0(const float* x, const float* ec, const float* eu, float scale, const int64_t* t,
                const float* tab_a, const float* tab_b, int mode, int N, int per_sample,
                float p_threshold, float* eps_out, float* x0_out, void* stream);
+/* Guidance on the model's own output, optional guidance rescale, eps and x0 for the step kernels and the dynamic
+ * threshold in ONE launch between the 2B forward and the step; not in the reference (Lin et al. 2023,
+ * arXiv:2305.08891 §3.4). It stands where dmc_pred_convert + dmc_cfg_x0 stand, and unlike them represents
+ * alphas_cumprod[t] = 0 for DMC_PRED_V (nothing divides). pc / pu: the conditional / unconditional rows, row n at
+ * pc + n*pc_stride (strides in floats, >= per_sample: the prediction half of a 2C-channel output is read in place);
+ * x, eps_out, x0_out: [N][per_sample]; sa = sqrt_alphas_cumprod, s1 = sqrt_one_minus_alphas_cumprod, [T]; t is clamped
+ * into [0, T). One block per sample; per element, each op rounded once, no fma:
+ *   d = pc - pu;  g = pu + scale*d                             -- dmc_cfg_x0's two roundings
+ *   rescale > 0:  g = g*f,  f = (float)(rescale*sqrt(M2_c/M2_g) + (1 - rescale)) in double, M2 = sum (v - mean)^2
+ *                 over the sample's pc (c) and g (g): two-pass double sums in a fixed order, no atomics. The ratio is
+ *                 std(pc)/std(g) under either normalisation. M2_g == 0: f = 1 (the public implementations give NaN)
+ *   DMC_PRED_V:   eps = s1*x + sa*g;  x0 = sa*x - s1*g         -- dmc_pred_convert's ops
+ *   DMC_PRED_EPS: eps = g;  x0 = (x - s1*g) / sa               -- dmc_cfg_x0 mode 0 with the tables' square roots
+ *   threshold on x0 as dmc_cfg_x0 (p_threshold < 1; <= 0: clamp +-1)
+ * rescale must lie in [0, 1]; 0 skips the reduction passes. eps_out may be NULL. per_sample > 16384 is refused before
+ * the launch. Accesses are element-wise. */
+int dmc_cfg_guide(int pred_type, const float* x, const float* pc, long pc_stride, const float* pu, long pu_stride,
+                  float scale, float rescale, const int64_t* t, const float* sa, const float* s1, int T, int N,
+                  int per_sample, float p_threshold, float* eps_out, float* x0_out, void* stream);
 
 /* Multi-tensor ops over a device array of descriptors {dst, src, n} (utils/trainer.py:187-202
  * EMA; :259 clip_grad_norm_). */
