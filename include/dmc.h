@@ -77,9 +77,11 @@ typedef struct dmc_conv_desc {
   const float* bias;         /* [Cout] or NULL */
   const float* addvec;       /* [N][ld_add] added per (n, co) (time/label embedding) or NULL */
   int ld_add;
-  const void* resid;         /* residual [pix][ld_res] in the output dtype, or NULL */
+  const void* resid;         /* residual [pix][ld_res] in the output dtype (with out_nchw: fp32 NCHW, laid out as y1),
+                              * or NULL. Added last before `act`: out = (acc + bias + addvec) * silu'(silu_pre) + resid */
   int ld_res;
-  const float* silu_pre;     /* if set, result *= silu'(silu_pre[pix][ld_silu]) (fp32) */
+  const float* silu_pre;     /* if set, (acc + bias + addvec) *= silu'(silu_pre[pix][ld_silu]) (fp32), before the
+                              * residual is added: a gradient accumulated in `resid` is not scaled by this SiLU */
   int ld_silu;
   int Csplit;                /* co < Csplit -> y1[pix*ldy1 + co], else y2[pix*ldy2 + co - Csplit] */
   int ldy1, ldy2;
