@@ -20,6 +20,9 @@
 //     8 waves runs 16-row tiles against them without another barrier;
 //   * staged (longer sequences): a 256-thread block per 64 rows re-stages 64-row tiles behind two
 //     barriers per tile.
+// Every kernel is instantiated for head-dim pads HDP = 32, 64 and 128 (dispatch()); the d guards of the
+// loads, the staging and the stores keep a head dim below its pad inside its row. fp32 at HDP = 128 has
+// no row-resident form (two 256-row images at a 528-byte pitch exceed the LDS): staged at every length.
 #include "dmc_common.h"
 #include "dmc_internal.h"
 
@@ -368,7 +371,13 @@ DMC_DEV void dq_store(const AttnK& a, int n, int hh, int q, const v4f* dq) {
   }
 }
 
-// dK/dV of the lane's key over queries [q0, q0+64): sL = log2-scaled lse (+inf past L -> P = 0), sDl = delta
+// dK/dV of the lane's key over queries [q0, q0+64): sL = log2-scaled lse (+inf past L -> P = 0), sDl = delta.
+// Up to a 64-wide pad (the else arm) the P and dS of all 64 queries are formed first and the two products follow.
+// Above it the 2 * DT accumulators alone are 64 registers, and the same work runs in KC passes of one key chunk each
+// (its 64 / KC queries' P and dS, then that chunk's products): half (bf16) the P / dS registers live, which keeps the
+// resident dropout kernel out of scratch. Every dk[dt] / dv[dt] still sums its chunks in the order kc = 0, 1, ..., so
+// both arms give the same bits. They are two arms, not one loop nest that makes a single pass for the narrow pads,
+// because that nest changes the schedule of the narrow kernels.
 template <typename T, int HDP, bool DROP = true>
 DMC_DEV void dkdv_queries(const AttnK& a, const char* sQ, const char* sD, const float* sL, const float* sDl,
                           const v4i* kf, const v4i* vf, float sl2, v4f* dk, v4f* dv, size_t ibase = 0,
@@ -379,35 +388,66 @@ DMC_DEV void dkdv_queries(const AttnK& a, const char* sQ, const char* sD, const 
   constexpr int KC = (sizeof(T) == 2) ? 2 : 4;
   constexpr int PITCH = HDP * sizeof(T) + 16;
   const int h = (threadIdx.x & 63) >> 4;
-  float p[4][4], ds[4][4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    v4f s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int dc = 0; dc < DC; ++dc) {
-      s = mma16<T>(s, lds_frag_rows(sQ, PITCH, 16 * t, dc * 64), kf[dc]);
-      dp = mma16<T>(dp, lds_frag_rows(sD, PITCH, 16 * t, dc * 64), vf[dc]);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int qi = 16 * t + 4 * h + i;   // query (row) within the tile
-      const float pv = ex2(s[i] * sl2 - sL[qi]);
-      if (DROP && a.dthresh) {   // ibase = index of (tile query 0, this key): query qi adds qi * L
-        const float mk = attn_keep(a, seed, ibase + (size_t)qi * a.L);
-        p[t][i] = pv * mk;
-        ds[t][i] = pv * (dp[i] * mk - sDl[qi]);
-      } else {
-        p[t][i] = pv;
-        ds[t][i] = pv * (dp[i] - sDl[qi]);
-      }
-    }
-  }
-#pragma unroll
-  for (int dt = 0; dt < DT; ++dt) {
+  if constexpr (HDP > 64) {
+    constexpr int TPC = 4 / KC;   // 16-query tiles per key chunk
 #pragma unroll
     for (int kc = 0; kc < KC; ++kc) {
-      dv[dt] = mma16<T>(dv[dt], tr_tok_frag<T, PITCH>(sD, kc, dt), acc_frag<T>(p, kc));
-      dk[dt] = mma16<T>(dk[dt], tr_tok_frag<T, PITCH>(sQ, kc, dt), acc_frag<T>(ds, kc));
+      float p[TPC][4], ds[TPC][4];
+#pragma unroll
+      for (int tt = 0; tt < TPC; ++tt) {
+        const int t = kc * TPC + tt;
+        v4f s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int dc = 0; dc < DC; ++dc) {
+          s = mma16<T>(s, lds_frag_rows(sQ, PITCH, 16 * t, dc * 64), kf[dc]);
+          dp = mma16<T>(dp, lds_frag_rows(sD, PITCH, 16 * t, dc * 64), vf[dc]);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int qi = 16 * t + 4 * h + i;
+          const float pv = ex2(s[i] * sl2 - sL[qi]);
+          const float mk = DROP && a.dthresh ? attn_keep(a, seed, ibase + (size_t)qi * a.L) : 1.f;
+          p[tt][i] = DROP ? pv * mk : pv;
+          ds[tt][i] = pv * ((DROP ? dp[i] * mk : dp[i]) - sDl[qi]);
+        }
+      }
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt) {
+        dv[dt] = mma16<T>(dv[dt], tr_tok_frag<T, PITCH>(sD, kc, dt), acc_frag<T>(p, 0));
+        dk[dt] = mma16<T>(dk[dt], tr_tok_frag<T, PITCH>(sQ, kc, dt), acc_frag<T>(ds, 0));
+      }
+    }
+  } else {
+    float p[4][4], ds[4][4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      v4f s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int dc = 0; dc < DC; ++dc) {
+        s = mma16<T>(s, lds_frag_rows(sQ, PITCH, 16 * t, dc * 64), kf[dc]);
+        dp = mma16<T>(dp, lds_frag_rows(sD, PITCH, 16 * t, dc * 64), vf[dc]);
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int qi = 16 * t + 4 * h + i;   // query (row) within the tile
+        const float pv = ex2(s[i] * sl2 - sL[qi]);
+        if (DROP && a.dthresh) {   // ibase = index of (tile query 0, this key): query qi adds qi * L
+          const float mk = attn_keep(a, seed, ibase + (size_t)qi * a.L);
+          p[t][i] = pv * mk;
+          ds[t][i] = pv * (dp[i] * mk - sDl[qi]);
+        } else {
+          p[t][i] = pv;
+          ds[t][i] = pv * (dp[i] - sDl[qi]);
+        }
+      }
+    }
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) {
+#pragma unroll
+      for (int kc = 0; kc < KC; ++kc) {
+        dv[dt] = mma16<T>(dv[dt], tr_tok_frag<T, PITCH>(sD, kc, dt), acc_frag<T>(p, kc));
+        dk[dt] = mma16<T>(dk[dt], tr_tok_frag<T, PITCH>(sQ, kc, dt), acc_frag<T>(ds, kc));
+      }
     }
   }
 }
@@ -704,11 +744,12 @@ __global__ __launch_bounds__(512) void attn_dkdv_res_kernel(AttnK a, int HG, int
 }
 
 // Heads per block of the resident kernels, 0 when the padded sequence exceeds kResRows rows (or the
-// staged kernels are forced with DMC_ATTN_STAGED). The largest divisor of heads that fits and still
-// leaves >= 256 blocks where the batch allows; DMC_ATTN_HG overrides the choice (tests).
-int res_heads(const AttnK& a, int* Lp) {
+// staged kernels are forced with DMC_ATTN_STAGED), or when the instantiation has no resident form
+// (`resident` false: fp32 above a 64-wide pad, see launch_all). The largest divisor of heads that fits and
+// still leaves >= 256 blocks where the batch allows; DMC_ATTN_HG overrides the choice (tests).
+int res_heads(const AttnK& a, int* Lp, bool resident = true) {
   *Lp = dmc::cdiv(a.L, 64) * 64;
-  if (*Lp > kResRows || dmc::opt(dmc::OPT_ATTN_STAGED)) return 0;
+  if (!resident || *Lp > kResRows || dmc::opt(dmc::OPT_ATTN_STAGED)) return 0;
   int hg = kResRows / *Lp;
   if (hg > a.heads) hg = a.heads;
   const long force = dmc::opt(dmc::OPT_ATTN_HG);
@@ -719,27 +760,32 @@ int res_heads(const AttnK& a, int* Lp) {
 
 template <typename T, int HDP>
 int launch_all(bool fwd, AttnK a, float* delta, hipStream_t s) {
+  // fp32 rows of a 128-wide pad are 528 bytes: two 256-row operand images would need 270 KB of the 160 KB LDS, so
+  // that case has no resident kernels (they are not instantiated) and runs the staged ones at every length
+  constexpr bool kResident = !(sizeof(T) == 4 && HDP > 64);
   int Lp;
-  const int hg = res_heads(a, &Lp);
+  const int hg = res_heads(a, &Lp, kResident);
   if (!fwd) { a.delta = delta; a.delta_out = delta; }
-  if (hg > 0) {
-    const int blocks = a.N * dmc::cdiv(a.heads, hg);
-    // DROP is a kernel parameter: without dropout the tile bodies have no per-element branches (which also split
-    // the MFMA / VALU schedule into basic blocks) and the register allocation is that path's alone
-    const bool drop = a.dthresh != 0;
-    if (fwd) {
-      if (drop) attn_fwd_res_kernel<T, HDP, true><<<blocks, 512, 0, s>>>(a, hg, Lp);
-      else attn_fwd_res_kernel<T, HDP, false><<<blocks, 512, 0, s>>>(a, hg, Lp);
-      return dmc::check_launch("dmc_attn_fwd");
+  if constexpr (kResident) {
+    if (hg > 0) {
+      const int blocks = a.N * dmc::cdiv(a.heads, hg);
+      // DROP is a kernel parameter: without dropout the tile bodies have no per-element branches (which also split
+      // the MFMA / VALU schedule into basic blocks) and the register allocation is that path's alone
+      const bool drop = a.dthresh != 0;
+      if (fwd) {
+        if (drop) attn_fwd_res_kernel<T, HDP, true><<<blocks, 512, 0, s>>>(a, hg, Lp);
+        else attn_fwd_res_kernel<T, HDP, false><<<blocks, 512, 0, s>>>(a, hg, Lp);
+        return dmc::check_launch("dmc_attn_fwd");
+      }
+      if (drop) {
+        attn_dq_res_kernel<T, HDP, true><<<blocks, 512, 0, s>>>(a, hg, Lp);
+        attn_dkdv_res_kernel<T, HDP, true><<<blocks, 512, 0, s>>>(a, hg, Lp);
+      } else {
+        attn_dq_res_kernel<T, HDP, false><<<blocks, 512, 0, s>>>(a, hg, Lp);
+        attn_dkdv_res_kernel<T, HDP, false><<<blocks, 512, 0, s>>>(a, hg, Lp);
+      }
+      return dmc::check_launch("dmc_attn_bwd");
     }
-    if (drop) {
-      attn_dq_res_kernel<T, HDP, true><<<blocks, 512, 0, s>>>(a, hg, Lp);
-      attn_dkdv_res_kernel<T, HDP, true><<<blocks, 512, 0, s>>>(a, hg, Lp);
-    } else {
-      attn_dq_res_kernel<T, HDP, false><<<blocks, 512, 0, s>>>(a, hg, Lp);
-      attn_dkdv_res_kernel<T, HDP, false><<<blocks, 512, 0, s>>>(a, hg, Lp);
-    }
-    return dmc::check_launch("dmc_attn_bwd");
   }
   dim3 g(dmc::cdiv(a.L, 64), a.N * a.heads);
   if (fwd) {
@@ -754,13 +800,17 @@ int launch_all(bool fwd, AttnK a, float* delta, hipStream_t s) {
 template <typename T>
 int dispatch(bool fwd, AttnK a, float* delta, hipStream_t s) {
   if (a.hd <= 32) return launch_all<T, 32>(fwd, a, delta, s);
-  return launch_all<T, 64>(fwd, a, delta, s);
+  if (a.hd <= 64) return launch_all<T, 64>(fwd, a, delta, s);
+  return launch_all<T, 128>(fwd, a, delta, s);
 }
 
+// Head dims: up to 64 a multiple of one 16-byte chunk (4 fp32 / 8 bf16 elements); above 64 and up to 128 a multiple
+// of 8 in both dtypes.
 int check(int dtype, int ld_qkv, int heads, int hd, int ld_out) {
   const int kpl = dtype == DMC_F32 ? 4 : 8;
   DMC_REQUIRE(dtype == DMC_F32 || dtype == DMC_BF16, "attn: dtype");
-  DMC_REQUIRE(hd > 0 && hd <= 64 && hd % kpl == 0, "attn: head dim %d must be <= 64 and a multiple of %d", hd, kpl);
+  DMC_REQUIRE(hd > 0 && hd <= 128 && hd % (hd > 64 ? 8 : kpl) == 0,
+              "attn: head dim %d must be a multiple of %d up to 64, or a multiple of 8 from 72 to 128", hd, kpl);
   DMC_REQUIRE(ld_qkv % kpl == 0 && ld_out % kpl == 0 && ld_qkv >= 3 * heads * hd, "attn: pitch alignment");
   DMC_REQUIRE(ld_out >= heads * hd, "attn: ld_out %d < heads * hd", ld_out);   // rows would overlap / run past the end
   return 0;

@@ -349,7 +349,8 @@ int dmc_channel_sum(int dtype, const void* dy, int N, int HW, int C, int ld, flo
 /* Self-attention of AttentionBlock (models/unet.py:84-99): qkv [N][L][ld_qkv] with channel
  * which*C + head*hd + d (reshape(B,3,heads,hd,HW)), softmax(QK^T/sqrt(hd))V -> out [N][L][ld_out]
  * channel head*hd + d; lse [N][heads][L] fp32 saved for backward.
- * hd <= 64, a multiple of the 16-byte chunk (4 fp32 / 8 bf16), as are ld_qkv >= 3*heads*hd and ld_out >= heads*hd;
+ * hd <= 64: a multiple of the 16-byte chunk (4 fp32 / 8 bf16); 64 < hd <= 128: a multiple of 8 in both dtypes
+ * (72, 80, ..., 128). ld_qkv >= 3*heads*hd and ld_out >= heads*hd are multiples of the 16-byte chunk;
  * ld_dqkv >= 3*heads*hd, a multiple of 4. Anything else is refused before a launch. */
 int dmc_attn_fwd(int dtype, const void* qkv, int ld_qkv, int N, int L, int heads, int hd, void* out,
                  int ld_out, float* lse, uint32_t drop_seed, const uint32_t* drop_seed_base,
