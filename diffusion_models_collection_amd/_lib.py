@@ -205,6 +205,10 @@ def _load():
                                 _c_p]),
         "dmc_cfg_guide": (_c_int, [_c_int, _c_p, _c_p, _c_long, _c_p, _c_long, _c_f, _c_f, _c_p, _c_p, _c_p, _c_int,
                                    _c_int, _c_int, _c_f, _c_p, _c_p, _c_p]),
+        "dmc_flow_step": (_c_int, [_c_p, _c_p, _c_long, _c_p, _c_long, _c_f, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int,
+                                   _c_int, _c_p, _c_p, _c_p, _c_p]),
+        "dmc_flow_guide": (_c_int, [_c_p, _c_p, _c_long, _c_p, _c_long, _c_f, _c_f, _c_p, _c_p, _c_int, _c_int, _c_int,
+                                    _c_int, _c_f, _c_p, _c_p]),
         "dmc_ema_update": (_c_int, [_c_p, _c_int, _c_f, _c_p]),
         "dmc_clip_grad_norm": (_c_int, [_c_p, _c_int, _c_f, _c_p, _c_p, _c_p]),
         "dmc_grad_norm_flat": (_c_int, [_c_p, _c_long, _c_f, _c_p, _c_p, _c_p, _c_p]),

@@ -13,7 +13,8 @@
 //   clip_grad_norm_     utils/trainer.py:259
 // Not in the reference: the DPM-Solver++ step (arXiv:2211.01095) and the v-prediction / min-SNR objective with its
 // output conversion (arXiv:2202.00512, arXiv:2303.09556), written to the same one-rounding-per-op rule, and the
-// variational-bound step of the bits-per-dimension evaluation (arXiv:2006.11239, arXiv:2102.09672).
+// variational-bound step of the bits-per-dimension evaluation (arXiv:2006.11239, arXiv:2102.09672), and the
+// rectified-flow Euler / Heun step with its guidance kernel (arXiv:2209.03003, arXiv:2206.00364).
 #include <stdlib.h>
 #include <string.h>
 #include "dmc_common.h"
@@ -1212,6 +1213,164 @@ __global__ __launch_bounds__(1024) void cfg_guide_kernel(int pred_type, const fl
   cfg_threshold(sv, x0_out + (size_t)n * per, per, npad, p);
 }
 
+// Rectified-flow ODE step (Liu et al. 2022, arXiv:2209.03003; Heun as Karras et al. 2022, arXiv:2206.00364 alg. 1):
+// guidance, Euler / Heun-predictor / Heun-corrector update and the history writes in one launch. diffusion/_flow.py
+// builds the rows {sigma, h, hh, kind} on the host; nothing here is transcendental and every op is a separate rounding.
+DMC_DEV float flow_velocity(float c, float u, bool guided, float scale) {
+  if (!guided) return c;
+  const float d = c - u;
+  return u + scale * d;
+}
+
+// Grid as dpm_step_kernel: blockIdx.y strides over samples, blockIdx.x over the sample's elements; the row index, its
+// step sizes and its kind are block-uniform, read once per sample. pc / pu rows sit at their own strides. VEC: 16-byte
+// accesses (per, pc_ld and pu_ld multiples of 4, every pointer 16-byte aligned). out may alias x, xb_out xb and d_out
+// dprev: an element is read before the same thread writes it.
+template <bool VEC>
+__global__ __launch_bounds__(256) void flow_step_kernel(const float* x, const float* pc, long pc_ld, const float* pu,
+                                                        long pu_ld, float scale, const float* xb, const float* dprev,
+                                                        const int64_t* step, const float* coef, int R, int N, int per,
+                                                        float* out, float* xb_out, float* d_out) {
+  const bool guided = pu != nullptr;
+  for (int n = blockIdx.y; n < N; n += gridDim.y) {
+    long s = step[n];
+    s = s < 0 ? 0 : (s > R - 1 ? R - 1 : s);   // never index past the table
+    const float* c = coef + s * 4;
+    const float h = c[1], hh = c[2], kf = c[3];
+    const int kind = kf == 1.f ? 1 : (kf == 2.f ? 2 : 0);
+    const bool hist = kind == 2 && xb != nullptr && dprev != nullptr;   // a corrector row without history: NaN out
+    const size_t base = (size_t)n * per;
+    const float* cr = pc + (size_t)n * pc_ld;
+    const float* ur = guided ? pu + (size_t)n * pu_ld : nullptr;
+    if (VEC) {
+      const int per4 = per / 4;
+      for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < per4; q += gridDim.x * blockDim.x) {
+        const size_t i = base + (size_t)q * 4;
+        const v4f cv = *(const v4f*)(cr + (size_t)q * 4);
+        v4f uv = {0.f, 0.f, 0.f, 0.f}, gv, ov;
+        if (guided) uv = *(const v4f*)(ur + (size_t)q * 4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) gv[k] = flow_velocity(cv[k], uv[k], guided, scale);
+        if (kind == 2) {
+          v4f bv = {NAN, NAN, NAN, NAN}, dv = bv;
+          if (hist) {
+            bv = *(const v4f*)(xb + i);
+            dv = *(const v4f*)(dprev + i);
+          }
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const float sum = dv[k] + gv[k];
+            ov[k] = bv[k] + hh * sum;
+          }
+        } else {
+          const v4f xv = *(const v4f*)(x + i);
+#pragma unroll
+          for (int k = 0; k < 4; ++k) ov[k] = xv[k] + h * gv[k];
+          if (kind == 1) {
+            if (xb_out) *(v4f*)(xb_out + i) = xv;
+            if (d_out) *(v4f*)(d_out + i) = gv;
+          }
+        }
+        *(v4f*)(out + i) = ov;
+      }
+    } else {
+      for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < per; q += gridDim.x * blockDim.x) {
+        const size_t i = base + q;
+        const float g = flow_velocity(cr[q], guided ? ur[q] : 0.f, guided, scale);
+        float o;
+        if (kind == 2) {
+          const float b = hist ? xb[i] : NAN, d = hist ? dprev[i] : NAN;
+          const float sum = d + g;
+          o = b + hh * sum;
+        } else {
+          const float xx = x[i];
+          o = xx + h * g;
+          if (kind == 1) {
+            if (xb_out) xb_out[i] = xx;
+            if (d_out) d_out[i] = g;
+          }
+        }
+        out[i] = o;
+      }
+    }
+  }
+}
+
+// Guided velocity of a rectified flow with the guidance rescale and / or the dynamic threshold of cfg_guide_kernel: one
+// block per sample, its launch shape, guide_block_sum2 and cfg_threshold unchanged. The threshold acts on the data
+// prediction x0 = x - sigma*g (sigma from the sample's coefficient row); g_out holds x0 in between, so it must not
+// alias x.
+__global__ __launch_bounds__(1024) void flow_guide_kernel(const float* x, const float* pc, long pc_ld, const float* pu,
+                                                          long pu_ld, float scale, float rescale, const int64_t* step,
+                                                          const float* coef, int R, int per, int npad, int threshold,
+                                                          float p, float* g_out) {
+  extern __shared__ double guide_sm[];   // the wave partials of the sums, then |x0| for the sort (>= 256 bytes)
+  float* sv = (float*)guide_sm;
+  const int n = blockIdx.x;
+  const float* cr = pc + (size_t)n * pc_ld;
+  const float* ur = pu + (size_t)n * pu_ld;
+  float* gr = g_out + (size_t)n * per;
+  long s = step[n];
+  s = s < 0 ? 0 : (s > R - 1 ? R - 1 : s);   // never index past the table
+  const float sigma = coef[s * 4];
+  float f = 1.0f;
+  if (rescale > 0.f) {
+    double sc = 0.0, sg = 0.0;
+    for (int i = threadIdx.x; i < per; i += blockDim.x) {
+      const float c = cr[i], u = ur[i];
+      const float d = c - u;
+      const float g = u + scale * d;
+      sc += (double)c;
+      sg += (double)g;
+    }
+    guide_block_sum2(sc, sg, guide_sm);
+    const double mc = sc / (double)per, mg = sg / (double)per;
+    double qc = 0.0, qg = 0.0;
+    for (int i = threadIdx.x; i < per; i += blockDim.x) {
+      const float c = cr[i], u = ur[i];
+      const float d = c - u;
+      const float g = u + scale * d;
+      const double dc = (double)c - mc, dg = (double)g - mg;
+      qc += dc * dc;
+      qg += dg * dg;
+    }
+    guide_block_sum2(qc, qg, guide_sm);
+    // a guided row without spread has no deviation to match: it is left as it is (f = 1)
+    if (qg > 0.0) f = (float)((double)rescale * sqrt(qc / qg) + (1.0 - (double)rescale));
+  }
+  if (!threshold) {   // block-uniform
+    for (int i = threadIdx.x; i < per; i += blockDim.x) {
+      const float c = cr[i], u = ur[i];
+      const float d = c - u;
+      float g = u + scale * d;
+      if (rescale > 0.f) g = g * f;
+      gr[i] = g;
+    }
+    return;
+  }
+  const float* xr = x + (size_t)n * per;
+  for (int i = threadIdx.x; i < npad; i += blockDim.x) {
+    float v = INFINITY;
+    if (i < per) {
+      const float c = cr[i], u = ur[i];
+      const float d = c - u;
+      float g = u + scale * d;
+      if (rescale > 0.f) g = g * f;
+      const float w = sigma * g;
+      const float x0 = xr[i] - w;
+      gr[i] = x0;
+      v = fabsf(x0);
+    }
+    sv[i] = v;
+  }
+  cfg_threshold(sv, gr, per, npad, p);
+  // cfg_threshold's last pass gave element i to thread i % blockDim.x, as this one does: no barrier in between
+  for (int i = threadIdx.x; i < per; i += blockDim.x) {
+    const float num = xr[i] - gr[i];
+    gr[i] = num / sigma;
+  }
+}
+
 // ---------------- multi-tensor ----------------
 __global__ void ema_kernel(const dmc_tensor_ref* refs, float decay) {
   const dmc_tensor_ref r = refs[blockIdx.y];
@@ -1753,6 +1912,48 @@ extern "C" int dmc_cfg_guide(int pred_type, const float* x, const float* pc, lon
   cfg_guide_kernel<<<N, 1024, lds, dmc::as_stream(stream)>>>(pred_type, x, pc, pc_stride, pu, pu_stride, scale, rescale,
                                                              t, sa, s1, T, per, npad, p, eps_out, x0_out);
   return dmc::check_launch("dmc_cfg_guide");
+}
+
+extern "C" int dmc_flow_step(const float* x, const float* pc, long pc_stride, const float* pu, long pu_stride,
+                             float scale, const float* xb, const float* dprev, const int64_t* step, const float* coef,
+                             int R, int N, int per, float* out, float* xb_out, float* d_out, void* stream) {
+  DMC_REQUIRE(R > 0 && N > 0 && per > 0, "flow_step: R %d, N %d, per_sample %d must be positive", R, N, per);
+  DMC_REQUIRE(x && pc && step && coef && out, "flow_step: x, pc, step, coef and out must not be NULL");
+  DMC_REQUIRE(pc_stride >= per && (!pu || pu_stride >= per), "flow_step: row strides %ld, %ld are below per_sample %d",
+              pc_stride, pu_stride, per);
+  const uintptr_t bits = (uintptr_t)x | (uintptr_t)pc | (uintptr_t)pu | (uintptr_t)xb | (uintptr_t)dprev |
+                         (uintptr_t)out | (uintptr_t)xb_out | (uintptr_t)d_out;   // a NULL operand adds no bits
+  const bool vec = per % 4 == 0 && pc_stride % 4 == 0 && (!pu || pu_stride % 4 == 0) && (bits & 15) == 0;
+  const int gx = grid_for(vec ? per / 4 : per);
+  const int gy_cap = 16384 / gx > 0 ? 16384 / gx : 1;
+  const dim3 grid(gx, N < gy_cap ? N : gy_cap);
+  hipStream_t s = dmc::as_stream(stream);
+  if (vec)
+    flow_step_kernel<true><<<grid, 256, 0, s>>>(x, pc, pc_stride, pu, pu_stride, scale, xb, dprev, step, coef, R, N, per,
+                                                out, xb_out, d_out);
+  else
+    flow_step_kernel<false><<<grid, 256, 0, s>>>(x, pc, pc_stride, pu, pu_stride, scale, xb, dprev, step, coef, R, N, per,
+                                                 out, xb_out, d_out);
+  return dmc::check_launch("dmc_flow_step");
+}
+
+extern "C" int dmc_flow_guide(const float* x, const float* pc, long pc_stride, const float* pu, long pu_stride,
+                              float scale, float rescale, const int64_t* step, const float* coef, int R, int N, int per,
+                              int threshold, float p, float* g_out, void* stream) {
+  DMC_REQUIRE(R > 0 && N > 0 && per > 0, "flow_guide: R %d, N %d, per_sample %d must be positive", R, N, per);
+  DMC_REQUIRE(pc && pu && step && coef && g_out, "flow_guide: pc, pu, step, coef and g_out must not be NULL");
+  DMC_REQUIRE(!threshold || (x && x != g_out), "flow_guide: the threshold needs x, in a buffer other than g_out");
+  DMC_REQUIRE(pc_stride >= per && pu_stride >= per, "flow_guide: row strides %ld, %ld are below per_sample %d", pc_stride,
+              pu_stride, per);
+  DMC_REQUIRE(rescale >= 0.f && rescale <= 1.f, "flow_guide: rescale %g is not in [0, 1]", (double)rescale);
+  DMC_REQUIRE(!(p >= 1.f), "flow_guide: p_threshold %g is not below 1", (double)p);
+  int npad = 1;
+  while (npad < per) npad <<= 1;
+  DMC_REQUIRE(npad <= 16384, "flow_guide: %d elements per sample exceeds 16384", per);
+  const size_t lds = npad * sizeof(float) < 256 ? 256 : npad * sizeof(float);   // 16 waves x 2 double partials
+  flow_guide_kernel<<<N, 1024, lds, dmc::as_stream(stream)>>>(x, pc, pc_stride, pu, pu_stride, scale, rescale, step, coef,
+                                                              R, per, npad, threshold ? 1 : 0, p, g_out);
+  return dmc::check_launch("dmc_flow_guide");
 }
 
 extern "C" int dmc_ema_update(const dmc_tensor_ref* refs, int count, float decay, void* stream) {

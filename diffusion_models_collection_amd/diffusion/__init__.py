@@ -1,8 +1,10 @@
-"""Diffusion schedulers (diffusion/__init__.py of the reference, plus the DPM-Solver++ sampler and the training-time
-timestep samplers)."""
+"""Diffusion schedulers (diffusion/__init__.py of the reference, plus the DPM-Solver++ sampler, the rectified flow and the
+training-time timestep samplers)."""
 from .ddpm import DDPM
 from .ddim import DDIM
 from .dpm_solver import DPMSolver
-from .resample import LossSecondMomentResampler, UniformSampler, create_named_schedule_sampler
+from .flow import RectifiedFlow
+from .resample import LogitNormalSampler, LossSecondMomentResampler, UniformSampler, create_named_schedule_sampler
 
-__all__ = ['DDPM', 'DDIM', 'DPMSolver', 'UniformSampler', 'LossSecondMomentResampler', 'create_named_schedule_sampler']
+__all__ = ['DDPM', 'DDIM', 'DPMSolver', 'RectifiedFlow', 'UniformSampler', 'LossSecondMomentResampler',
+           'LogitNormalSampler', 'create_named_schedule_sampler']

@@ -15,10 +15,16 @@ only the multiset enters sqrt(mean_k h^2).
 dmc_ts_history_update and dmc_ts_sample (kernels.ts_history_update, kernels.ts_sample) do on the device what the two
 functions here do on the host; nothing in training calls these: they are the statement the tests check the kernels
 against, kept beside the checks the samplers use.
+
+The logit-normal density (Esser et al. 2024, arXiv:2403.03206 §3.1) is not loss-aware and needs no kernel: its exact bin
+masses and their CDF are built here once (logit_normal_masses, logit_normal_cdf) and the draw is one searchsorted on the
+device table.
 """
+import math
+
 import numpy as np
 
-SAMPLERS = ("uniform", "loss-second-moment")
+SAMPLERS = ("uniform", "loss-second-moment", "logit-normal")
 
 
 def check_sampler_name(name):
@@ -76,3 +82,40 @@ def second_moment_weights(hist, count, uniform_prob):
 def draw(cdf, u):
     """dmc_ts_sample's draw: the smallest i with cdf[i] > u."""
     return np.minimum(np.searchsorted(cdf, u, side="right"), len(cdf) - 1).astype(np.int64)
+
+
+def check_logit_normal(mean, std):
+    for name, v in (("mean", mean), ("std", std)):
+        if isinstance(v, (bool, str, bytes)) or not isinstance(v, (int, float, np.integer, np.floating)) \
+                or not math.isfinite(float(v)):
+            raise ValueError(f"logit-normal {name} must be a finite number, got {v!r}")
+    if not float(std) > 0.0:
+        raise ValueError(f"logit-normal std must be > 0, got {std!r}")
+    return float(mean), float(std)
+
+
+def logit_normal_masses(num_timesteps, mean=0.0, std=1.0):
+    """p_t = Phi((logit((t+1)/T) - mean)/std) - Phi((logit(t/T) - mean)/std) in float64, t in [0, T): the mass a
+    logit-normal variable on (0, 1) puts on the bin [t/T, (t+1)/T), with logit(0) = -inf and logit(1) = +inf. The
+    differences are taken on the side of the mean where Phi is small (Phi(a) - Phi(b) = Phi(-b) - Phi(-a)), so the tail
+    bins keep their relative precision."""
+    T = int(num_timesteps)
+    if T < 1:
+        raise ValueError(f"num_timesteps must be >= 1, got {num_timesteps!r}")
+    mean, std = check_logit_normal(mean, std)
+    z = np.empty(T + 1, np.float64)
+    z[0], z[T] = -np.inf, np.inf
+    e = np.arange(1, T, dtype=np.float64) / T
+    z[1:T] = (np.log(e) - np.log1p(-e) - mean) / std
+    phi = np.vectorize(lambda v: 0.5 * math.erfc(-v / math.sqrt(2.0)), otypes=[np.float64])
+    lo, hi = z[:-1], z[1:]
+    upper = lo >= 0                       # the bin lies above the mean: work with the upper tails
+    return np.where(upper, phi(-lo) - phi(-hi), phi(hi) - phi(lo))
+
+
+def logit_normal_cdf(masses):
+    """fp32 [T]: the float64 running sum of the masses rounded once, the last entry 1 (what the total is, up to the
+    rounding of T additions)."""
+    cdf = np.cumsum(np.asarray(masses, np.float64)).astype(np.float32)
+    cdf[-1] = 1.0
+    return np.ascontiguousarray(cdf)

@@ -14,6 +14,9 @@ deterministic given the draws. _resample.py has the formulas and their host rest
 With several ranks each rank keeps the history of its own losses and weights by the p it drew from, so each rank's
 estimator stays unbiased; gathering the losses across ranks (as the paper's code does) is not done. The history is
 not part of the trainer's checkpoints: a resumed run draws uniformly until K * T losses have re-warmed it.
+
+'logit-normal' (LogitNormalSampler) is the fixed density rectified flows are trained with (arXiv:2403.03206 §3.1): no
+state, no importance weights, one searchsorted per draw.
 """
 import torch
 
@@ -127,8 +130,62 @@ class LossSecondMomentResampler:
         count.copy_(c)
 
 
+class LogitNormalSampler:
+    """t from the logit-normal density of Esser et al. 2024 (arXiv:2403.03206 §3.1), which puts the training weight on
+    the middle noise levels of a rectified flow: u = sigmoid(mean + std * z), z ~ N(0, 1), t = floor(u * T). The exact
+    bin masses and their CDF are built once on the host (_resample.logit_normal_masses); a draw is torch.rand and one
+    torch.searchsorted on the device table. The loss is NOT re-weighted (the density is the weighting, as in SD3), so
+    weight_table() is None and every weight is 1. Works with any scheduler object that has num_timesteps."""
+
+    def __init__(self, diffusion, mean=0.0, std=1.0):
+        self.num_timesteps = int(diffusion.num_timesteps)
+        self.mean, self.std = _resample.check_logit_normal(mean, std)
+        self._device = getattr(diffusion, "device", "cuda")
+        self._masses = _resample.logit_normal_masses(self.num_timesteps, self.mean, self.std)
+        self._cdf_host = torch.from_numpy(_resample.logit_normal_cdf(self._masses))
+        self._cdf = None
+
+    def cdf(self, device=None):
+        """fp32 [T] on the device, uploaded once per device."""
+        dev = torch.device(self._device if device is None else device)
+        if self._cdf is None or self._cdf.device != dev:
+            self._cdf = self._cdf_host.to(dev)
+        return self._cdf
+
+    def sample(self, batch_size, device=None, u=None):
+        """(t int64 [B], weights fp32 [B] of ones). u: the draws in [0, 1) to use (fp32 [B]), torch.rand's by default;
+        t is the smallest index whose CDF entry exceeds u."""
+        cdf = self.cdf(device)
+        if u is None:
+            u = torch.rand(batch_size, dtype=torch.float32, device=cdf.device)
+        elif u.numel() != batch_size:
+            raise ValueError(f"u holds {u.numel()} draws for a batch of {batch_size}")
+        t = torch.searchsorted(cdf, u.to(cdf.device).float().contiguous().view(-1), right=True)
+        return t.clamp_(max=self.num_timesteps - 1), torch.ones(batch_size, dtype=torch.float32, device=cdf.device)
+
+    def update_with_local_losses(self, t, losses):
+        pass
+
+    def weights(self):
+        """p [T], an fp32 tensor on the sampler's device, as LossSecondMomentResampler.weights()."""
+        return torch.from_numpy(self._masses.astype("float32")).to(torch.device(self._device))
+
+    def weight_table(self):
+        """None: every importance weight is 1."""
+        return None
+
+    def state_dict(self):
+        return {}
+
+    def load_state_dict(self, state):
+        pass
+
+
 def create_named_schedule_sampler(name, diffusion, **kwargs):
-    """'uniform' or 'loss-second-moment' (kwargs: history_per_term, uniform_prob)."""
-    if _resample.check_sampler_name(name) == "uniform":
+    """'uniform', 'loss-second-moment' (kwargs: history_per_term, uniform_prob) or 'logit-normal' (kwargs: mean, std)."""
+    name = _resample.check_sampler_name(name)
+    if name == "uniform":
         return UniformSampler(diffusion, **kwargs)
+    if name == "logit-normal":
+        return LogitNormalSampler(diffusion, **kwargs)
     return LossSecondMomentResampler(diffusion, **kwargs)

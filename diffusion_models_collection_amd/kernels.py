@@ -1117,6 +1117,68 @@ def cfg_guide(pred_type, x, pc, pu, scale, rescale, t, sa, s1, p_threshold, want
     return eps, x0
 
 
+def _flow_coef(what, coef, dev):
+    if (coef is None or coef.dim() != 2 or coef.shape[1] != 4 or coef.shape[0] < 1 or coef.dtype != torch.float32
+            or coef.device != dev or not coef.is_contiguous()):
+        got = "None" if coef is None else f"{coef.dtype} {tuple(coef.shape)} on {coef.device}"
+        raise L.DMCError(f"{what}: coef must be a contiguous fp32 [R, 4] tensor on {dev}, got {got}")
+    return coef.shape[0]
+
+
+def flow_step(x, pc, step, coef, pu=None, scale=1.0, xb=None, dprev=None, out=None, xb_out=None, d_out=None):
+    """Rectified-flow ODE update (dmc_flow_step): step[n] picks sample n's row {sigma, h, hh, kind} of the [R, 4] table
+    (diffusion/_flow.py). pc / pu: the conditional / unconditional velocities, x's shape, contiguous or row-strided views
+    (the halves of the 2B-row model output) read in place; pu None: no guidance. xb / dprev: the Heun history a corrector
+    row reads, xb_out / d_out: where a predictor row leaves it (either may be the tensor it replaces; None: not written).
+    out may be x. Returns out."""
+    what = "dmc_flow_step"
+    if x is None or not x.is_cuda or x.dim() < 1 or x.numel() < 1:
+        got = "None" if x is None else f"{tuple(x.shape)} on {x.device}"
+        raise L.DMCError(f"{what}: x must be a non-empty device tensor, got {got}")
+    N = x.shape[0]
+    ldc = _row_stride(what, pc, x)
+    ldu = _row_stride(what, pu, x) if pu is not None else 0
+    if out is None:
+        out = torch.empty_like(x)
+    _same(x, xb, dprev, out, xb_out, d_out, what=what)
+    _fp32_contig(what, x, xb, dprev, out, xb_out, d_out)
+    if step is None:
+        raise L.DMCError(f"{what}: needs a step index")
+    _steps(N, x.device, step, what=what)
+    R = _flow_coef(what, coef, x.device)
+    check(LIB.dmc_flow_step(ptr(x), ptr(pc), ldc, ptr(pu), ldu, float(scale), ptr(xb), ptr(dprev), ptr(step), ptr(coef),
+                            R, N, x.numel() // N, ptr(out), ptr(xb_out), ptr(d_out), L.stream()), what)
+    return out
+
+
+def flow_guide(x, pc, pu, scale, rescale, step, coef, threshold=False, p_threshold=None, out=None):
+    """Guided velocity of a rectified flow (dmc_flow_guide) with the guidance rescale of arXiv:2305.08891 (rescale in
+    [0, 1], 0: none) and, with threshold=True, the dynamic threshold on the data prediction x - sigma*g (p_threshold in
+    (0, 1): quantile, None: clamp to +-1). pc / pu as flow_step; out must not be x. Returns out, flow_step's pc."""
+    what = "dmc_flow_guide"
+    if x is None or not x.is_cuda or x.dim() < 1 or x.numel() < 1:
+        got = "None" if x is None else f"{tuple(x.shape)} on {x.device}"
+        raise L.DMCError(f"{what}: x must be a non-empty device tensor, got {got}")
+    N = x.shape[0]
+    ldc, ldu = _row_stride(what, pc, x), _row_stride(what, pu, x)
+    if out is None:
+        out = torch.empty_like(x)
+    _same(x, out, what=what)
+    _fp32_contig(what, x, out)
+    if out.data_ptr() == x.data_ptr():
+        raise L.DMCError(f"{what}: out must not be x")
+    if step is None:
+        raise L.DMCError(f"{what}: needs a step index")
+    _steps(N, x.device, step, what=what)
+    R = _flow_coef(what, coef, x.device)
+    if not 0.0 <= float(rescale) <= 1.0:
+        raise L.DMCError(f"{what}: rescale {rescale!r} is not in [0, 1]")
+    p = float(p_threshold) if p_threshold is not None else -1.0
+    check(LIB.dmc_flow_guide(ptr(x), ptr(pc), ldc, ptr(pu), ldu, float(scale), float(rescale), ptr(step), ptr(coef), R,
+                             N, x.numel() // N, int(bool(threshold)), p, ptr(out), L.stream()), what)
+    return out
+
+
 class TensorRefs:
     """Device array of dmc_tensor_ref {a, b, n} for the multi-tensor kernels (uploaded once per pointer set)."""
 

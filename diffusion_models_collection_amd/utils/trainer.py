@@ -288,6 +288,8 @@ class GraphedTrainStep:
                 and (not trainer.is_distributed or trainer.grad_sync is not None)
                 and trainer._flat is not None and trainer.gradient_accumulation_steps == 1
                 and getattr(trainer, "schedule_sampler", None) is None      # the sampler's two launches run eager
+                # a process the captured step has no objective for (RectifiedFlow) opts out; absent: as before
+                and getattr(trainer.diffusion, "graphed_train_step", True)
                 and _is_dmc_model(trainer._raw_model))
 
     def _key(self, images, y):

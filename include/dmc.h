@@ -597,6 +597,34 @@ int dmc_cfg_x0(const float* x, const float* ec, const float* eu, float scale, co
 int dmc_cfg_guide(int pred_type, const float* x, const float* pc, long pc_stride, const float* pu, long pu_stride,
                   float scale, float rescale, const int64_t* t, const float* sa, const float* s1, int T, int N,
                   int per_sample, float p_threshold, float* eps_out, float* x0_out, void* stream);
+/* Rectified-flow ODE step (not in the reference; Liu et al. 2022, arXiv:2209.03003, Heun's scheme as Karras et al. 2022,
+ * arXiv:2206.00364 alg. 1): guidance, update and history in ONE launch beside the model. coef: [R][4] fp32 rows
+ * {sigma, h, hh, kind} (diffusion/_flow.py: h = sigma_next - sigma, hh = h/2); step[n] in [0,R) picks sample n's row (an
+ * index outside is clamped into the table); a kind other than 1 or 2 is 0. pc / pu: the conditional / unconditional
+ * velocity rows, row n at pc + n*pc_stride (strides in floats, >= per_sample: the halves of a 2N-row model output are
+ * read in place); pu NULL: no guidance. Per element, each op rounded once, no fma:
+ *   g = pu ? pu + scale*(pc - pu) : pc                          -- dmc_cfg_x0's two roundings
+ *   kind 0 (Euler):      out = x + h*g
+ *   kind 1 (predictor):  out = x + h*g;  xb_out = x;  d_out = g -- each written only if its pointer is given
+ *   kind 2 (corrector):  out = xb + hh*(dprev + g)              -- x is not read
+ * Rows of kind 0 or 1 never read xb or dprev (either may be NULL or hold NaN), rows of kind 0 or 2 never write xb_out or
+ * d_out; a kind-2 row with xb or dprev NULL gives NaN. out may be the same buffer as x, xb_out as xb, d_out as dprev.
+ * 16-byte accesses when per_sample and both strides are multiples of 4 and every pointer is 16-byte aligned,
+ * element-wise otherwise. */
+int dmc_flow_step(const float* x, const float* pc, long pc_stride, const float* pu, long pu_stride, float scale,
+                  const float* xb, const float* dprev, const int64_t* step, const float* coef, int R, int N,
+                  int per_sample, float* out, float* xb_out, float* d_out, void* stream);
+/* Guided velocity of a rectified flow when the guidance is rescaled or the data prediction thresholded (otherwise
+ * dmc_flow_step guides by itself); g_out feeds dmc_flow_step as pc with pu NULL. One block per sample, dmc_cfg_guide's
+ * launch shape, sums and threshold; operands and row choice as dmc_flow_step. Per element, each op rounded once:
+ *   g = pu + scale*(pc - pu);  rescale > 0: g = g*f, f exactly as dmc_cfg_guide forms it
+ *   threshold == 0:  g_out = g                                  -- x is not read
+ *   threshold != 0:  x0 = x - sigma*g;  the threshold of dmc_cfg_x0 on x0 (p_threshold in (0,1): quantile; <= 0: clamp
+ *                    +-1);  g_out = (x - x0) / sigma            -- sigma of the sample's row; g_out must not be x
+ * rescale must lie in [0, 1]. per_sample > 16384 is refused before the launch. Accesses are element-wise. */
+int dmc_flow_guide(const float* x, const float* pc, long pc_stride, const float* pu, long pu_stride, float scale,
+                   float rescale, const int64_t* step, const float* coef, int R, int N, int per_sample, int threshold,
+                   float p_threshold, float* g_out, void* stream);
 
 /* Multi-tensor ops over a device array of descriptors {dst, src, n} (utils/trainer.py:187-202
  * EMA; :259 clip_grad_norm_). */
