@@ -254,6 +254,18 @@ def _load():
         "dmc_selective_scan_bwd": (_c_int, [_c_int, _c_p, _c_int, _c_p, _c_int, _c_p, _c_int, _c_p, _c_int, _c_p, _c_p,
                                             _c_int, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p,
                                             _c_int, _c_p, _c_int, _c_p, _c_int, _c_p, _c_int, _c_int, _c_p, _c_p, _c_p]),
+        "dmc_scan_order_token": (_c_int, [_c_int, _c_int, _c_int, _c_int]),
+        "dmc_causal_conv_silu_fwd_ord": (_c_int, [_c_int, _c_p, _c_int, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int,
+                                                  _c_int, _c_p, _c_int, _c_p]),
+        "dmc_causal_conv_silu_bwd_ord": (_c_int, [_c_int, _c_p, _c_int, _c_p, _c_int, _c_p, _c_p, _c_int, _c_int, _c_int,
+                                                  _c_int, _c_int, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p]),
+        "dmc_selective_scan_fwd_ord": (_c_int, [_c_int, _c_p, _c_int, _c_p, _c_int, _c_p, _c_int, _c_p, _c_p, _c_int,
+                                                _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p,
+                                                _c_p, _c_p, _c_int, _c_p]),
+        "dmc_selective_scan_bwd_ord": (_c_int, [_c_int, _c_p, _c_int, _c_p, _c_int, _c_p, _c_int, _c_p, _c_int, _c_p,
+                                                _c_p, _c_int, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int,
+                                                _c_int, _c_p, _c_p, _c_p, _c_int, _c_p, _c_int, _c_p, _c_int, _c_p,
+                                                _c_int, _c_int, _c_p, _c_p, _c_p]),
         "dmc_load_batch": (_c_int, [_c_p, _c_long, _c_int, _c_int, _c_int, _c_p, _c_int, _c_p, _c_u32, _c_u32, _c_long,
                                     ctypes.POINTER(_c_f), ctypes.POINTER(_c_f), _c_p, _c_p, _c_p, _c_p]),
     }

@@ -33,6 +33,39 @@ enum Opt {
 long opt(Opt o);
 }  // namespace dmc
 
+// Scan orders of the DiM Mamba mixer over the h x w token grid. order: bit 0 reverse, bit 1
+// column-major, bit 2 snake (every other line walked backwards). A logical position p in [0, h*w) is q = reverse ?
+// h*w-1-p : p, line a = q / inner, place b = q % inner (inner = column ? h : w); dmc_order_token_ab is the token
+// (row-major index i*w + j) at (a, b), so a kernel that walks p by +-1 carries (a, b) and maps each position it reaches without a division.
+namespace dmc {
+// mul / shift: q / inner for 0 <= q < 2^31 as (q * mul) >> shift, exact (shift = 31 + ceil(log2 inner), mul =
+// ceil(2^shift / inner) <= 2^32 + 1: the error term q * (mul * inner - 2^shift) / (inner * 2^shift) is below 1 / inner),
+// so the kernels never run an integer division. make_scan_ord fills them on the host.
+struct ScanOrd { int h, w, order, shift; unsigned long long mul; };
+__host__ __device__ inline int order_inner(ScanOrd o) { return (o.order & 2) ? o.h : o.w; }
+inline ScanOrd make_scan_ord(int h, int w, int order) {
+  ScanOrd o{h, w, order, 31, 0};
+  const unsigned long long d = (unsigned long long)order_inner(o);
+  while ((1ull << (o.shift - 31)) < d) ++o.shift;
+  o.mul = ((1ull << o.shift) + d - 1) / d;
+  return o;
+}
+__host__ __device__ inline int order_token_ab(ScanOrd o, int a, int b) {
+  if ((o.order & 4) && (a & 1)) b = order_inner(o) - 1 - b;
+  return (o.order & 2) ? b * o.w + a : a * o.w + b;
+}
+// 0 <= q < h*w -> a = q / inner, b = q % inner
+__host__ __device__ inline void order_line(ScanOrd o, int q, int& a, int& b) {
+  a = (int)(((unsigned long long)(unsigned)q * o.mul) >> o.shift);
+  b = q - a * order_inner(o);
+}
+__host__ __device__ inline int order_token(ScanOrd o, int p) {   // 0 <= p < h*w
+  int a, b;
+  order_line(o, (o.order & 1) ? o.h * o.w - 1 - p : p, a, b);
+  return order_token_ab(o, a, b);
+}
+}  // namespace dmc
+
 #define DMC_REQUIRE(cond, ...)       \
   do {                               \
     if (!(cond)) {                   \

@@ -1383,3 +1383,45 @@ def selective_scan_bwd(dtype, dy, ld_dy, u, ld_u, z, ld_z, z_col, dpre, ld_dp, b
                                      ptr(D), ptr(dt_bias), B, L_, E, N, ptr(states), ptr(ws), ptr(du), ld_du,
                                      _col_ptr(dz, dz_col), ld_dz, ptr(ddpre), ld_ddp, ptr(dbc), ld_dbc, bc_col,
                                      ptr(dA_log), ptr(dD), L.stream()), "dmc_selective_scan_bwd")
+
+
+# ---- scan orders: the same ops over the h x w token grid walked in order `order` (a 3-bit code, models/dim.py) ----
+def scan_order_token(order, h, w, p):
+    """The token (row index within an image) at logical position p of the walk `order` over the h x w grid."""
+    t = LIB.dmc_scan_order_token(order, h, w, p)
+    if t < 0:
+        raise L.DMCError(f"dmc_scan_order_token: order {order}, grid {h} x {w}, position {p}")
+    return t
+
+
+def causal_conv_silu_fwd_ord(dtype, x, ld_x, w, bias, B, h, wt, order, E, u, ld_u, x_col=0):
+    check(LIB.dmc_causal_conv_silu_fwd_ord(L.dtype_code(dtype), _col_ptr(x, x_col), ld_x, ptr(w), ptr(bias), B, h, wt,
+                                           order, E, ptr(u), ld_u, L.stream()), "dmc_causal_conv_silu_fwd_ord")
+
+
+def causal_conv_silu_bwd_ord(dtype, du, ld_du, x, ld_x, w, bias, B, h, wt, order, E, dx, ld_dx, dw, dbias, x_col=0,
+                             dx_col=0):
+    ws = SCRATCH.get(LIB.dmc_causal_conv_workspace(B, h * wt, E), du.device)
+    check(LIB.dmc_causal_conv_silu_bwd_ord(L.dtype_code(dtype), ptr(du), ld_du, _col_ptr(x, x_col), ld_x, ptr(w),
+                                           ptr(bias), B, h, wt, order, E, _col_ptr(dx, dx_col), ld_dx, ptr(dw),
+                                           ptr(dbias), ptr(ws), L.stream()), "dmc_causal_conv_silu_bwd_ord")
+
+
+def selective_scan_fwd_ord(dtype, u, ld_u, z, ld_z, z_col, dpre, ld_dp, bc, ld_bc, b_col, c_col, A_log, D, dt_bias, B,
+                           h, wt, order, E, N, states, y, ld_y):
+    ws = SCRATCH.get(LIB.dmc_selective_scan_workspace(B, h * wt, E, N, 0), u.device) if states is not None else None
+    check(LIB.dmc_selective_scan_fwd_ord(L.dtype_code(dtype), ptr(u), ld_u, _col_ptr(z, z_col), ld_z, ptr(dpre), ld_dp,
+                                         _col_ptr(bc, b_col), _col_ptr(bc, c_col), ld_bc, ptr(A_log), ptr(D),
+                                         ptr(dt_bias), B, h, wt, order, E, N, ptr(states), ptr(ws), ptr(y), ld_y,
+                                         L.stream()), "dmc_selective_scan_fwd_ord")
+
+
+def selective_scan_bwd_ord(dtype, dy, ld_dy, u, ld_u, z, ld_z, z_col, dpre, ld_dp, bc, ld_bc, b_col, c_col, A_log, D,
+                           dt_bias, B, h, wt, order, E, N, states, du, ld_du, dz, ld_dz, dz_col, ddpre, ld_ddp, dbc,
+                           ld_dbc, bc_col, dA_log, dD):
+    ws = SCRATCH.get(LIB.dmc_selective_scan_workspace(B, h * wt, E, N, 1), u.device)
+    check(LIB.dmc_selective_scan_bwd_ord(L.dtype_code(dtype), ptr(dy), ld_dy, ptr(u), ld_u, _col_ptr(z, z_col), ld_z,
+                                         ptr(dpre), ld_dp, _col_ptr(bc, b_col), _col_ptr(bc, c_col), ld_bc, ptr(A_log),
+                                         ptr(D), ptr(dt_bias), B, h, wt, order, E, N, ptr(states), ptr(ws), ptr(du),
+                                         ld_du, _col_ptr(dz, dz_col), ld_dz, ptr(ddpre), ld_ddp, ptr(dbc), ld_dbc,
+                                         bc_col, ptr(dA_log), ptr(dD), L.stream()), "dmc_selective_scan_bwd_ord")

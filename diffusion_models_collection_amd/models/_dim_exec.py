@@ -23,6 +23,10 @@ up to 8):
   out = y out_proj^T                             [T, H]
 The backward mirrors it: dmc_selective_scan_bwd recomputes the states chunk by chunk from the saved chunk-entry
 states; every projection's gradients are the conv dgrad / wgrad kernels.
+
+Scan orders (model.scan_orders, one 3-bit code per block): the conv and the scan are the only two ops that know the
+token order, so a block with a non-zero code calls their _ord entry points with (ht, wt, code) and everything else,
+every buffer included, is as for code 0. A block with code 0 calls exactly what it called before there were orders.
 """
 import torch
 
@@ -50,6 +54,7 @@ class DiMExecutor(TokenExecutor):
     def __init__(self, model):
         H = model.hidden_size
         self.mixer = model.mixer
+        self.scan_orders = tuple(getattr(model, "scan_orders", ())) or (0,) * len(model.blocks)
         if self.mixer == "attention":
             self.in_proj = [_W(b.mamba_block.mamba.in_proj_weight) for b in model.blocks]
         else:
@@ -133,7 +138,11 @@ class DiMExecutor(TokenExecutor):
         xz = self._new(B, ht, wt, 2 * E)
         self._conv([Act(h1, ht, wt, H)], mm.in_proj, K.TAPS1, ht, wt, 2 * E, out=xz.t)
         u = self._new(B, ht, wt, E)
-        K.causal_conv_silu_fwd(dt, xz.t, 2 * E, mm.conv1d.weight, mm.conv1d.bias, B, Lt, E, u.t, E)
+        code = self.scan_orders[i]
+        if code:
+            K.causal_conv_silu_fwd_ord(dt, xz.t, 2 * E, mm.conv1d.weight, mm.conv1d.bias, B, ht, wt, code, E, u.t, E)
+        else:
+            K.causal_conv_silu_fwd(dt, xz.t, 2 * E, mm.conv1d.weight, mm.conv1d.bias, B, Lt, E, u.t, E)
         # x_proj as two GEMMs over u: dt_low in the compute dtype (a GEMM operand next), Bm | Cm in fp32
         Kc = L.kc_for(E, dt)
         dtl = torch.empty(B, ht, wt, R8, dtype=dt, device=dev)
@@ -144,8 +153,12 @@ class DiMExecutor(TokenExecutor):
         self._conv([Act(dtl, ht, wt, R)], mm.dt_proj, K.TAPS1, ht, wt, E, out=dpre, out_f32=True)
         states = K.scan_states(B, Lt, E, N, dev)
         yg = self._new(B, ht, wt, E)
-        K.selective_scan_fwd(dt, u.t, E, xz.t, 2 * E, E, dpre, E, bc, 2 * N, 0, N, mm.A_log, mm.D, mm.dt_proj.bias,
-                             B, Lt, E, N, states, yg.t, E)
+        if code:
+            K.selective_scan_fwd_ord(dt, u.t, E, xz.t, 2 * E, E, dpre, E, bc, 2 * N, 0, N, mm.A_log, mm.D,
+                                     mm.dt_proj.bias, B, ht, wt, code, E, N, states, yg.t, E)
+        else:
+            K.selective_scan_fwd(dt, u.t, E, xz.t, 2 * E, E, dpre, E, bc, 2 * N, 0, N, mm.A_log, mm.D, mm.dt_proj.bias,
+                                 B, Lt, E, N, states, yg.t, E)
         ao = self._new(B, ht, wt, H)
         self._conv([yg], mm.out_proj, K.TAPS1, ht, wt, H, out=ao.t)
         return ao, (xz, u, dtl, bc, dpre, states, yg)
@@ -162,9 +175,15 @@ class DiMExecutor(TokenExecutor):
         dyg = new(E)
         self._conv([Act(dao, ht, wt, H)], mm.out_proj, K.TAPS1, ht, wt, E, out=dyg, packmode=L.PACK_DGRAD)
         du_s, dxz, ddpre, dbc, ddtl = new(E), new(2 * E), new(E), new(2 * N), new(R8)
-        K.selective_scan_bwd(dt, dyg, E, u.t, E, xz.t, 2 * E, E, dpre, E, bc, 2 * N, 0, N, mm.A_log, mm.D,
-                             mm.dt_proj.bias, B, Lt, E, N, states, du_s, E, dxz, 2 * E, E, ddpre, E, dbc, 2 * N, 0,
-                             gv(mm.A_log), gv(mm.D))
+        code = self.scan_orders[i]
+        if code:
+            K.selective_scan_bwd_ord(dt, dyg, E, u.t, E, xz.t, 2 * E, E, dpre, E, bc, 2 * N, 0, N, mm.A_log, mm.D,
+                                     mm.dt_proj.bias, B, ht, wt, code, E, N, states, du_s, E, dxz, 2 * E, E, ddpre, E,
+                                     dbc, 2 * N, 0, gv(mm.A_log), gv(mm.D))
+        else:
+            K.selective_scan_bwd(dt, dyg, E, u.t, E, xz.t, 2 * E, E, dpre, E, bc, 2 * N, 0, N, mm.A_log, mm.D,
+                                 mm.dt_proj.bias, B, Lt, E, N, states, du_s, E, dxz, 2 * E, E, ddpre, E, dbc, 2 * N, 0,
+                                 gv(mm.A_log), gv(mm.D))
         # dt_proj: dpre = dt_low W^T (+ bias inside the scan, so its gradient is the column sum of ddpre)
         self._wgrad([Act(dtl, ht, wt, R)], ddpre, E, K.TAPS1, ht, wt, E, gv(mm.dt_proj.weight),
                     dbias=gv(mm.dt_proj.bias))
@@ -177,8 +196,12 @@ class DiMExecutor(TokenExecutor):
         du = new(E)
         self._conv([Act(ddtl, ht, wt, R8), Act(dbc, ht, wt, 2 * N)], None, K.TAPS1, ht, wt, E, out=du,
                    w=self._xproj_pack(i, "dgrad"), Kc=L.kc_for(R8 + 2 * N, dt), resid=du_s)
-        K.causal_conv_silu_bwd(dt, du, E, xz.t, 2 * E, mm.conv1d.weight, mm.conv1d.bias, B, Lt, E, dxz, 2 * E,
-                               gv(mm.conv1d.weight), gv(mm.conv1d.bias))
+        if code:
+            K.causal_conv_silu_bwd_ord(dt, du, E, xz.t, 2 * E, mm.conv1d.weight, mm.conv1d.bias, B, ht, wt, code, E, dxz,
+                                       2 * E, gv(mm.conv1d.weight), gv(mm.conv1d.bias))
+        else:
+            K.causal_conv_silu_bwd(dt, du, E, xz.t, 2 * E, mm.conv1d.weight, mm.conv1d.bias, B, Lt, E, dxz, 2 * E,
+                                   gv(mm.conv1d.weight), gv(mm.conv1d.bias))
         self._wgrad([Act(h1, ht, wt, H)], dxz, 2 * E, K.TAPS1, ht, wt, 2 * E, gv(mm.in_proj.weight))
         dh1 = torch.empty(B, ht, wt, H, dtype=torch.float32, device=dev)
         self._conv([Act(dxz, ht, wt, 2 * E)], mm.in_proj, K.TAPS1, ht, wt, H, out=dh1, packmode=L.PACK_DGRAD,

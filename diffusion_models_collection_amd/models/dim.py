@@ -19,7 +19,16 @@ model_params); without it the constructor raises NotImplementedError and says ho
     unverified.
 
 The modules are parameter containers; the arithmetic is `_dim_exec.DiMExecutor` on libdmc.so.
-Extra (optional) constructor arguments: compute_dtype = "fp32" | "bf16" (as models/unet.py), mixer.
+Extra (optional) constructor arguments: compute_dtype = "fp32" | "bf16" (as models/unet.py), mixer, scan.
+
+scan (mixer="mamba" only, not in the reference): the order in which each block's causal conv and selective scan walk
+the h x w patch grid. The reference walks every block in row-major order, so information only ever flows forward
+along that one path; DiM (Teng et al., arXiv:2405.14224) and ZigMa (Hu et al., arXiv:2403.13802) change the order from
+block to block instead, with no extra parameters. An order is a 3-bit code (bit 0 reverse, bit 1 column-major, bit 2
+snake: every other line walked backwards, so consecutive tokens are always grid neighbours), named in SCAN_ORDERS;
+scan is a pattern name of SCAN_PATTERNS, cycled over the blocks, or a sequence of `depth` order names. "row" (the
+default) is the reference's behaviour, bit for bit. The kernels walk the order in place; the
+state_dict does not change.
 """
 import math
 from typing import Tuple
@@ -31,6 +40,14 @@ from .dit import LabelEmbedder, PatchEmbed, TimestepEmbedder, _KernelOnly
 from .unet import _resolve_dtype
 
 _MIXERS = ("mamba", "attention")
+# scan orders by name: the index is the code (bit 0 reverse, bit 1 column-major, bit 2 snake)
+SCAN_ORDERS = ("row", "row_rev", "col", "col_rev", "snake_row", "snake_row_rev", "snake_col", "snake_col_rev")
+SCAN_PATTERNS = {
+    "row": ("row",),
+    "bidir": ("row", "row_rev"),
+    "cross": ("row", "row_rev", "col", "col_rev"),                                # DiM's four sweeps
+    "zigzag": ("snake_row", "snake_col", "snake_row_rev", "snake_col_rev"),       # after ZigMa
+}
 _ATTN_HEADS = 8     # the reference's fallback: nn.MultiheadAttention(hidden, num_heads=8) (dim.py:112-117)
 
 
@@ -130,8 +147,63 @@ def _resolve_mixer(mixer):
     return mixer
 
 
+def _order_code(order):
+    if isinstance(order, str):
+        if order not in SCAN_ORDERS:
+            raise DMCError(f"DiM: scan order {order!r} (one of {SCAN_ORDERS})")
+        return SCAN_ORDERS.index(order)
+    if isinstance(order, bool) or not isinstance(order, int) or not 0 <= order < len(SCAN_ORDERS):
+        raise DMCError(f"DiM: scan order {order!r} (a name of {SCAN_ORDERS} or its code 0..7)")
+    return order
+
+
+def scan_permutation(order, h, w):
+    """LongTensor perm [h*w]: perm[p] = the token (row-major index i*w + j) at logical position p of the order (a name
+    of SCAN_ORDERS or its code) over the h x w grid. x[:, perm] are the tokens in walking order; the C library's
+    dmc_scan_order_token is the same mapping."""
+    code = _order_code(order)
+    if h < 1 or w < 1:
+        raise DMCError(f"DiM: scan_permutation over a {h} x {w} grid")
+    Lt = h * w
+    p = torch.arange(Lt, dtype=torch.long)
+    q = Lt - 1 - p if code & 1 else p
+    inner = h if code & 2 else w
+    a, b = q // inner, q % inner
+    if code & 4:
+        b = torch.where(a % 2 == 1, inner - 1 - b, b)
+    i, j = (b, a) if code & 2 else (a, b)
+    return i * w + j
+
+
+def resolve_scan(scan, depth, mixer="mamba"):
+    """scan (a pattern name of SCAN_PATTERNS or a sequence of `depth` order names) -> the tuple of per-block codes."""
+    if isinstance(scan, str):
+        if scan not in SCAN_PATTERNS:
+            raise DMCError(f"DiM: scan {scan!r} (a pattern of {tuple(SCAN_PATTERNS)}, or a sequence of one order name "
+                           f"of {SCAN_ORDERS} per block)")
+        pat = SCAN_PATTERNS[scan]
+        codes = tuple(SCAN_ORDERS.index(pat[i % len(pat)]) for i in range(depth))
+    else:
+        try:
+            names = list(scan)
+        except TypeError:
+            raise DMCError(f"DiM: scan {scan!r} (a pattern of {tuple(SCAN_PATTERNS)}, or a sequence of one order "
+                           "name per block)") from None
+        if len(names) != depth:
+            raise DMCError(f"DiM: scan gives {len(names)} orders for depth {depth} (one per block)")
+        try:
+            codes = tuple(_order_code(n) for n in names)
+        except RuntimeError as e:
+            raise DMCError(f"DiM: scan {names!r}: {e}") from None
+    if mixer == "attention" and any(codes):
+        raise DMCError(f"DiM(mixer='attention'): scan {scan!r}; attention has no token order to change (every token "
+                       "attends to every other, and the position embedding is all that tells them apart): scan must "
+                       "be 'row'")
+    return codes
+
+
 class DiM(nn.Module):
-    """Diffusion Mamba (dim.py:208-346); the reference's arguments plus compute_dtype and mixer."""
+    """Diffusion Mamba (dim.py:208-346); the reference's arguments plus compute_dtype, mixer and scan."""
 
     def __init__(
         self,
@@ -147,8 +219,10 @@ class DiM(nn.Module):
         compute_dtype=None,
         mixer=None,
         learn_sigma=False,
+        scan="row",
     ):
         mixer = _resolve_mixer(mixer)
+        scan_orders = resolve_scan(scan, depth, mixer)
         dt = _resolve_dtype(compute_dtype)
         if isinstance(img_size, int):
             img_size = (img_size, img_size)
@@ -178,6 +252,8 @@ class DiM(nn.Module):
         self.dropout = dropout
         self.mlp_ratio = mlp_ratio
         self.mixer = mixer
+        self.scan = scan if isinstance(scan, str) else tuple(SCAN_ORDERS[c] for c in scan_orders)
+        self.scan_orders = scan_orders     # per block: the 3-bit code the mixer kernels get (0 = the reference's order)
         self.num_heads = _ATTN_HEADS
         self.compute_dtype = dt
 

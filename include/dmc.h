@@ -758,14 +758,29 @@ int dmc_ln_affine_mod_bwd(int dtype, const void* dh, int ld_dh, const float* x, 
  *   the channels) as columns bc_col .. bc_col + 2N of the rows dbc (pitch ld_dbc; the columns behind them up to the
  *   pitch are zeroed); dA_log [E][N] and dD [E] (sums over images and tokens). No atomics: every sum has a fixed
  *   order. workspace: dmc_selective_scan_workspace(.., 1) bytes. The dt_proj bias gradient is the column sum of
- *   ddpre (the weight-gradient kernel's wg_bias). */
+ *   ddpre (the weight-gradient kernel's wg_bias).
+ * Scan orders (the _ord entry points): the tokens of an image are the h x w patch grid in row-major rows, and the
+ *   recurrence walks them in another order -- "permute the tokens, run the op, un-permute", done by address arithmetic
+ *   inside the kernels. order is a 3-bit code: bit 0 reverse, bit 1 column-major, bit 2 snake (every other line
+ *   walked backwards). dmc_scan_order_token(order, h, w, p) is the token (row index within the image) at logical
+ *   position p of the walk: q = reverse ? h*w-1-p : p; inner = column ? h : w; a = q / inner, b = q % inner;
+ *   snake and a odd: b = inner-1-b; (i, j) = column ? (b, a) : (a, b); token = i*w + j. -1 for arguments out of
+ *   range. Order 0 is the identity. The _ord entry points take (h, w, order) in place of L = h*w; every other
+ *   argument, the workspaces and `states` (sized for L = h*w) are those of the plain entry points, which stay the
+ *   order-0 code path. */
 int dmc_causal_conv_silu_fwd(int dtype, const void* x, int ld_x, const float* w, const float* bias, int B, int L, int E,
                              void* u, int ld_u, void* stream);
 size_t dmc_causal_conv_workspace(int B, int L, int E);
 int dmc_causal_conv_silu_bwd(int dtype, const void* du, int ld_du, const void* x, int ld_x, const float* w,
                              const float* bias, int B, int L, int E, void* dx, int ld_dx, float* dw, float* dbias,
                              void* workspace, void* stream);
+int dmc_causal_conv_silu_fwd_ord(int dtype, const void* x, int ld_x, const float* w, const float* bias, int B, int h,
+                                 int wt, int order, int E, void* u, int ld_u, void* stream);
+int dmc_causal_conv_silu_bwd_ord(int dtype, const void* du, int ld_du, const void* x, int ld_x, const float* w,
+                                 const float* bias, int B, int h, int wt, int order, int E, void* dx, int ld_dx,
+                                 float* dw, float* dbias, void* workspace, void* stream);
 int dmc_scan_chunk(void);
+int dmc_scan_order_token(int order, int h, int w, int p);
 size_t dmc_selective_scan_workspace(int B, int L, int E, int N, int backward);
 int dmc_selective_scan_fwd(int dtype, const void* u, int ld_u, const void* z, int ld_z, const float* dpre, int ld_dp,
                            const float* Bm, const float* Cm, int ld_bc, const float* A_log, const float* D,
@@ -776,6 +791,16 @@ int dmc_selective_scan_bwd(int dtype, const void* dy, int ld_dy, const void* u, 
                            const float* D, const float* dt_bias, int B, int L, int E, int N, const float* states,
                            void* workspace, void* du, int ld_du, void* dz, int ld_dz, void* ddpre, int ld_ddp,
                            void* dbc, int ld_dbc, int bc_col, float* dA_log, float* dD, void* stream);
+int dmc_selective_scan_fwd_ord(int dtype, const void* u, int ld_u, const void* z, int ld_z, const float* dpre,
+                               int ld_dp, const float* Bm, const float* Cm, int ld_bc, const float* A_log,
+                               const float* D, const float* dt_bias, int B, int h, int w, int order, int E, int N,
+                               float* states, void* workspace, void* y, int ld_y, void* stream);
+int dmc_selective_scan_bwd_ord(int dtype, const void* dy, int ld_dy, const void* u, int ld_u, const void* z, int ld_z,
+                               const float* dpre, int ld_dp, const float* Bm, const float* Cm, int ld_bc,
+                               const float* A_log, const float* D, const float* dt_bias, int B, int h, int w, int order,
+                               int E, int N, const float* states, void* workspace, void* du, int ld_du, void* dz,
+                               int ld_dz, void* ddpre, int ld_ddp, void* dbc, int ld_dbc, int bc_col, float* dA_log,
+                               float* dD, void* stream);
 
 /* ---- Device-resident data path (datasets/base_dataset.py:96-128, train.py:107-128) ----
  * One training batch from a uint8 image bank [n_images][H][W][C] resident in device memory: out[b] =
